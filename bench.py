@@ -7,10 +7,17 @@ MFMA DotInteraction, top MLP), mean BCE, backward (fused re-gather interaction b
 dense SGD and the fused sparse SGD apply on the embedding slab (the reference's DLRM SGD path,
 ctr/train.py:77-79). Inputs are pre-generated on device (no host I/O in the timed region).
 
-Usage: python bench.py [--gpus N --steps K --warmup W]. N > 1: under torch.distributed.run
-(WORLD_SIZE must equal N), or, when WORLD_SIZE is unset, bench.py launches torch.distributed.run
-with N ranks itself as a child process before touching the GPU and exits with its status.
-Prints ONE JSON line on rank 0.
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]. N > 1: under
+torch.distributed.run (WORLD_SIZE must equal N), or, when WORLD_SIZE is unset, bench.py launches
+torch.distributed.run with N ranks itself as a child process before touching the GPU and exits
+with its status. Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step). --full
+adds every secondary measurement to the line, each in a run of its own around the timed steps:
+the PMC traffic passes, the per-step distribution, the in-step kernel spans, the layer-by-layer
+MLP step times, the embedding-path roofline, the Keras Adam line, weak scaling (N > 1) and the CPU
+baseline (--pmc, --compare-layerwise, --keras-line, --weak-secondary and --cpu-baseline-steps
+select among them). --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -34,6 +41,7 @@ from recommender_amd.ctr.train import TrainStep, build_model  # noqa: E402
 from recommender_amd.synthetic import criteo_batch, criteo_cardinalities  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+PACE = 16  # the timed loop keeps at most 2 x PACE steps in flight (see main)
 WATCH = ["rs_dlrm_train_step_fwd_unit", "rs_dlrm_train_step_fwd_unit_nofold",
          "rs_dlrm_interaction_fwd", "rs_dlrm_interaction_fwd_head",
          "rs_dlrm_interaction_fwd_head_dx",
@@ -77,6 +85,14 @@ def parse():
     # SURVEY 8(d) timing method: warm-up 10, measure 100 steps (0.1 s of GPU time)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (PMC traffic, step distribution, "
+                         "in-step kernel spans, layerwise MLP, roofline, Keras Adam, weak scaling, "
+                         "CPU baseline); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (loss, "
+                         "predictions, the updated MLP parameters, a seeded sample of the updated "
+                         "table rows) as DIR/<name>.npy, float32 / float64, under 64 MB in all")
     ap.add_argument("--batch", type=int, default=65536,
                     help="global batch (strong scaling) or per-GPU batch (--scaling weak)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
@@ -429,6 +445,51 @@ def cpu_baseline(args, cards):
                       f"of {n_meas} ({med:.3f} s/step, {sum(times):.1f} s timed)"}
 
 
+DUMP_ARRAY_BYTES = 2 << 20   # per array (12 MLP parameters + predictions: under 32 MB)
+DUMP_TABLE_BYTES = 16 << 20  # the sample of table rows
+
+
+def dump_outputs(path, args, model, step, loss, batch):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32
+    <name>.npy files (row numbers as float64): the step's loss and per-example predictions, every
+    MLP parameter as the step's update left it, and the table rows the step's batch touched. An
+    array over its byte budget is cut to a sample drawn by a generator seeded with --seed (sorted
+    flat indices; whole rows for the table), so two runs with the same arguments write the same
+    elements. The caller has synchronised the device: the step's deferred update has landed."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng([args.seed, 64])
+
+    def save(name, t):
+        a = t.detach().reshape(-1)
+        cap = DUMP_ARRAY_BYTES // 4
+        if a.numel() > cap:
+            pick = np.sort(rng.choice(a.numel(), cap, replace=False))
+            a = a[torch.from_numpy(pick).to(a.device)]
+        elif t.dim() > 0:
+            a = t.detach()
+        np.save(os.path.join(path, name + ".npy"), a.to("cpu", torch.float32).numpy())
+
+    save("loss", loss.reshape(1))
+    save("predictions", step.last_pred)
+    for n, p in model.named_parameters():
+        if not n.endswith("grad_handle"):
+            save("param." + n, p)
+    emb = model.embedding_layer
+    so = getattr(emb, "slot_offsets", None)
+    if isinstance(getattr(emb, "weight", None), torch.Tensor) and so is not None:
+        # the slab rows of the batch's ids (slot offset + id), distinct and ascending; a
+        # row-sharded slab (--gpus > 1) is not sampled
+        ids = batch[0].reshape(-1, so.numel() - 1).to(torch.int64)
+        rows = torch.unique(ids + so[:-1])
+        keep = max(1, DUMP_TABLE_BYTES // (4 * emb.weight.shape[1]))
+        if rows.numel() > keep:
+            pick = np.sort(rng.choice(rows.numel(), keep, replace=False))
+            rows = rows[torch.from_numpy(pick).to(rows.device)]
+        np.save(os.path.join(path, "embedding_row_ids.npy"), rows.cpu().numpy().astype(np.float64))
+        np.save(os.path.join(path, "embedding_rows.npy"),
+                emb.weight[rows].to("cpu", torch.float32).numpy())
+
+
 def launch_ranks(args) -> int:
     """--gpus N > 1 without an external launcher: run torch.distributed.run with N ranks as a
     child process (this process has not touched the GPU) and return its exit status."""
@@ -455,7 +516,7 @@ def main():
     MLP.factored_backward = args.mlp_bwd == "factored"
     MLP.composed_forward = args.mlp_fwd == "composed"
     traffic, traffic_detail = None, None
-    if args.pmc and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+    if args.full and args.pmc and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         traffic, traffic_detail = measure_traffic(args)  # before any GPU initialisation
     world, rank, local = init_dist(args)
     requested_batch = args.batch
@@ -495,8 +556,9 @@ def main():
                      fused=bool(args.fused), comm=comm, defer_sparse_join=bool(args.defer_join),
                      defer_decay=bool(args.defer_decay))
     pool = make_pool(args, cards, rank, dev)
-    # the PMC child counts one launch of each path kernel per step: no extra sorts here
-    U = 0.0 if args.pmc_child else measured_unique(pool, model)
+    # the PMC child counts one launch of each path kernel per step: no extra sorts here (and a
+    # plain run, which reports no roofline, does not need the count)
+    U = measured_unique(pool, model) if args.full and not args.pmc_child else 0.0
 
     if args.prio:
         hp = torch.cuda.Stream(device=dev, priority=-1)
@@ -526,8 +588,8 @@ def main():
         runners = [step.capture_sequence(pool)]
         singles = [step.capture(b) for b in pool]
         per_call = len(pool)
-    # the timed steps run with no per-kernel instrumentation; the in-step kernel spans
-    # (`kernels`) come from a second, instrumented pass over the same steps afterwards
+    # the timed steps run with no per-kernel instrumentation; with --full the in-step kernel
+    # spans (`kernels`) come from a second, instrumented pass over the same steps afterwards
     timer = L.KernelTimer(WATCH)
     torch.cuda.synchronize()
     barrier(world)
@@ -541,7 +603,21 @@ def main():
         for i in range(args.steps % per_call):
             loss = singles[i]()
     else:
+        # the host issues a step faster than the GPU runs it, and every step in flight holds its
+        # own gradient-row buffers (they are handed to the side stream and return to the
+        # allocator only once that stream has passed them): unpaced, a long run queues hundreds
+        # of steps, fills the device memory and then stalls in the allocator's free-and-retry, by
+        # an amount that differs from run to run. So the loop keeps at most 2 x PACE steps in
+        # flight, as a training loop that reads its loss now and then does: every PACE steps it
+        # records an event and waits for the one recorded PACE steps earlier (long since reached
+        # unless the host is that far ahead; the GPU's queue never runs dry)
+        pace = [torch.cuda.Event(), torch.cuda.Event()]
         for i in range(args.steps):
+            if i % PACE == 0:
+                k = (i // PACE) % 2
+                if i >= 2 * PACE:
+                    pace[k].synchronize()
+                pace[k].record()
             loss = runners[i % len(runners)]()
     ev1.record()
     torch.cuda.synchronize()
@@ -566,6 +642,11 @@ def main():
         wall += materialize_ms * 1e-3
     ms_step = wall / args.steps * 1e3
     value = args.batch * world * args.steps / wall
+    if args.dump_outputs and rank == 0:
+        # before any secondary pass steps the model further
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, args, model, step, loss, pool[(args.steps - 1) % P])
+    barrier(world)
     if args.pmc_child:  # the counters cover the warm-up + timed steps only
         if world > 1:
             dist.destroy_process_group()
@@ -596,7 +677,7 @@ def main():
     # step starts on the main stream (the deferred update overlaps the next step, so this is the
     # steady-state step time), reported as p10 / median / p90 (SURVEY 8(d) timing method)
     step_dist = None
-    if per_call == 1 and args.steps >= 4:
+    if args.full and per_call == 1 and args.steps >= 4:
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
         for i in range(args.steps):
             evs[i].record()
@@ -610,20 +691,21 @@ def main():
                      "ms": raw}
 
     # instrumented pass: HIP-event span of every watched kernel inside the steps
-    L.set_timer(timer)
-    timer.enabled = True
-    if per_call > 1:
-        for _ in range(args.steps // per_call):
-            loss = runners[0]()
-    else:
-        for i in range(args.steps):
-            loss = runners[i % len(runners)]()
-    torch.cuda.synchronize()
-    timer.enabled = False
-    L.set_timer(None)
+    if args.full:
+        L.set_timer(timer)
+        timer.enabled = True
+        if per_call > 1:
+            for _ in range(args.steps // per_call):
+                loss = runners[0]()
+        else:
+            for i in range(args.steps):
+                loss = runners[i % len(runners)]()
+        torch.cuda.synchronize()
+        timer.enabled = False
+        L.set_timer(None)
 
     layerwise_ms = layerwise_fwd_ms = None
-    if args.compare_layerwise and args.mlp_bwd == "factored" and not args.graph:
+    if args.full and args.compare_layerwise and args.mlp_bwd == "factored" and not args.graph:
         if args.mlp_fwd == "composed":
             layerwise_fwd_ms = time_variant(True, False)
         layerwise_ms = time_variant(False, False)
@@ -646,7 +728,7 @@ def main():
     per_ex = S * (8 + 8 * D) + S * (8 + 4 * D) + (U / args.batch) * 8 * D
     path_bytes = per_ex * args.batch
     roof = None
-    if world == 1 and D == 128 and args.fused and args.mlp_fwd == "composed":
+    if args.full and world == 1 and D == 128 and args.fused and args.mlp_fwd == "composed":
         iso = isolated_path(model, pool[0][0])
         path_us = sum(iso.values())
         a = path_bytes / (path_us * 1e-6) / 1e9
@@ -701,7 +783,7 @@ def main():
     # the same model and batches, with the deferred exact decay (bit-identical to the per-step
     # dense sweep after materialize(); tests/test_northstar_gpu.py), for the record
     keras = None
-    if world == 1 and args.keras_line and args.optimizer == "sgd" and not args.graph:
+    if args.full and world == 1 and args.keras_line and args.optimizer == "sgd" and not args.graph:
         torch.cuda.synchronize()
         kstep = TrainStep(model, "keras_adam", lr=1e-3, fused=True, defer_sparse_join=True,
                           defer_decay=True)
@@ -741,7 +823,7 @@ def main():
 
     # N > 1 under strong scaling: the same step at --batch per GPU (weak scaling), for the record
     weak = None
-    if world > 1 and args.scaling == "strong" and args.weak_secondary:
+    if args.full and world > 1 and args.scaling == "strong" and args.weak_secondary:
         wpool = make_pool(args, cards, rank, dev, batch=requested_batch)
         WP = len(wpool)
         emb = model.embedding_layer
@@ -772,7 +854,7 @@ def main():
         del wpool
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_baseline_steps > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline_steps > 0:
         cpu = cpu_baseline(args, cards)
 
     if rank == 0:
@@ -780,6 +862,7 @@ def main():
             "metric": "examples/sec fwd+bwd, Criteo-DLRM 26×40M×128 batch 65536, 1/2/4/8 GPU",
             "value": round(value, 1), "unit": "examples/sec", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
+            "full": bool(args.full),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "fp32",
             "step_ms_distribution": step_dist,
             "data": "synthetic (Criteo-Kaggle-skewed 26-slot slab, bounded Zipf(1.05) ids, seed 4)",

@@ -118,6 +118,64 @@ def test_graph_keras_adam_flat_layout_cpu():
     assert torch.all(opt.grad_flat[pad_mask] == 0)
 
 
+def test_bench_plain_run_is_the_default_and_full_is_opt_in(monkeypatch):
+    import sys
+
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_bench_dump_outputs_files_budget_and_repeatability(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on host tensors: float32 / float64 .npy files of the loss, the
+    predictions, every parameter and the batch's table rows; an array over its budget is cut to
+    the same seeded sample on every call."""
+    import argparse
+    import os
+
+    import torch
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_ARRAY_BYTES", 4 * 100)
+    monkeypatch.setattr(bench, "DUMP_TABLE_BYTES", 4 * 8 * 5)
+    g = torch.Generator().manual_seed(4)
+    model = torch.nn.Module()
+    model.lin = torch.nn.Linear(30, 20)  # weight: 600 elements, over the 100-element budget
+    model.embedding_layer = torch.nn.Module()
+    model.embedding_layer.grad_handle = torch.nn.Parameter(torch.zeros(0))
+    model.embedding_layer.register_buffer("weight", torch.rand(40, 8, generator=g))
+    model.embedding_layer.register_buffer("slot_offsets", torch.tensor([0, 10, 40]))
+    step = argparse.Namespace(last_pred=torch.rand(16, generator=g))
+    cat = torch.stack([torch.randint(0, 10, (16,), generator=g),
+                       torch.randint(0, 30, (16,), generator=g)], 1)
+    args = argparse.Namespace(seed=4)
+    got = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), args, model, step, torch.tensor(0.5), (cat, None, None))
+        got.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = got
+    assert set(a) == {"loss.npy", "predictions.npy", "param.lin.weight.npy", "param.lin.bias.npy",
+                      "embedding_row_ids.npy", "embedding_rows.npy"}
+    for f in a:
+        assert a[f].dtype == (np.float64 if f == "embedding_row_ids.npy" else np.float32), f
+        np.testing.assert_array_equal(a[f], b[f])
+    assert a["loss.npy"].tolist() == [0.5]
+    np.testing.assert_array_equal(a["predictions.npy"], step.last_pred.numpy())
+    np.testing.assert_array_equal(a["param.lin.bias.npy"], model.lin.bias.detach().numpy())
+    w = model.lin.weight.detach().numpy().reshape(-1)
+    assert a["param.lin.weight.npy"].shape == (100,) and np.isin(a["param.lin.weight.npy"], w).all()
+    rows = a["embedding_row_ids.npy"].astype(np.int64)
+    touched = np.unique(cat.numpy() + np.array([0, 10]))
+    assert rows.shape == (5,) and (np.diff(rows) > 0).all() and np.isin(rows, touched).all()
+    np.testing.assert_array_equal(a["embedding_rows.npy"], model.embedding_layer.weight.numpy()[rows])
+
+
 def test_bench_pmc_filter_keeps_every_family_main_kernel():
     """bench.py's PMC passes filter kernels by PMC_KERNEL_REGEX and count each family's calls by
     its main kernel: a main kernel the filter drops leaves the family at 0 calls and the line's

@@ -1,15 +1,18 @@
-# A/B of the north-star step's stream schedule (run under gpurun): each variant is one bench.py
+# A/B of the north-star step's stream schedule on one GPU box: each variant is one bench.py --full
 # run without the PMC / secondary lines; prints ms/step (median, p10) and the in-step spans.
+# Files go to $OUT (default out/).
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+OUT=${OUT:-out}
+export OUT
+mkdir -p $OUT
 run() {  # name, env..., -- bench args
   name=$1; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" timeout -k 10 300 python bench.py --pmc 0 --keras-line 0 --weak-secondary 0 \
-    --compare-layerwise 0 --cpu-baseline-steps 0 --steps 200 "$@" > gpurun_out/stepab_$name.json 2> gpurun_out/stepab_$name.err || { echo "$name failed"; tail -5 gpurun_out/stepab_$name.err; return 1; }
+  env "${envs[@]}" timeout -k 10 300 python bench.py --full --pmc 0 --keras-line 0 --weak-secondary 0 \
+    --compare-layerwise 0 --cpu-baseline-steps 0 --steps 200 "$@" > $OUT/stepab_$name.json 2> $OUT/stepab_$name.err || { echo "$name failed"; tail -5 $OUT/stepab_$name.err; return 1; }
   python - "$name" <<'PY'
-import json, sys
-d = json.loads(open(f"gpurun_out/stepab_{sys.argv[1]}.json").read().strip().splitlines()[-1])
+import json, os, sys
+d = json.loads(open(f"{os.environ['OUT']}/stepab_{sys.argv[1]}.json").read().strip().splitlines()[-1])
 k = d.get("kernels") or {}
 dist = d.get("step_ms_distribution") or {}
 print(f"{sys.argv[1]:14s} ms/step {d['ms_per_step']:.4f} median {dist.get('median')} "
