@@ -790,8 +790,11 @@ struct SegSlot {
 
 // The host picks this form from max_slot_rows (<= 2^24); the widths come from the device
 // offsets. A slot wider than 2^24 rows (offsets that disagree with the host's bound) would need
-// w1 > 12 and overrun the 4096-bin LDS arrays: the widths are clamped to 12 (no overrun), the
-// output is not sorted, and RS_ERRBIT_RANGE is raised instead.
+// w1 > 12, and an id >= 2^24 a pass-1 digit (id >> w0) past the 4096-bin LDS arrays. Such a slot
+// is cut to its first 2^24 rows: w1 is clamped to 12 and the ids beyond become sentinels in pass
+// 0 (seg_load0 compares with sl.rows; RS_ERRBIT_OOB as for any id outside its slot), so every id
+// that reaches pass 1 is < 2^24 and its digit < 4096 with no per-key test there. The output is
+// not the sort of the declared table, and RS_ERRBIT_RANGE says so (Embedding.check_errors).
 __device__ __forceinline__ SegSlot seg_slot(const SegArgs& a, int s) {
   SegSlot r;
   r.lo = a.slot_offsets ? a.slot_offsets[s] : 0;
@@ -801,6 +804,7 @@ __device__ __forceinline__ SegSlot seg_slot(const SegArgs& a, int s) {
   r.w1 = bits - r.w0;
   if (r.w1 > kSegBits) {
     r.w1 = kSegBits;
+    r.rows = (int64_t)1 << kSegMaxBits;
     if (threadIdx.x == 0 && a.err_flag) atomicOr(a.err_flag, RS_ERRBIT_RANGE);
   }
   return r;

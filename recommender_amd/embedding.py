@@ -19,6 +19,17 @@ from . import _lib as L
 from .functional import embedding_lookup
 
 
+def check_err_flag(err_flag: torch.Tensor) -> int:
+    """The bits of a kernel error flag (device int32 [1]; synchronises). RS_ERRBIT_RANGE — the
+    slot-segmented sort met a slot wider than the max_slot_rows it was given, so what it wrote
+    is not the sort of the ids — raises: nothing computed from that sort can be used."""
+    bits = int(err_flag.item())
+    if bits & L.RS_ERRBIT_RANGE:
+        raise RuntimeError("RS_ERRBIT_RANGE: slot wider than max_slot_rows allows; "
+                           "sort output invalid")
+    return bits
+
+
 class Embedding(nn.Module):
     def __init__(self, input_dim: int, output_dim: int, mask_zero: bool = False, device=None,
                  slot_offsets: torch.Tensor | None = None, init_range: float = 0.05,
@@ -215,9 +226,15 @@ class Embedding(nn.Module):
     def zero_grad_pending(self):
         self._pending = []
 
+    def check_errors(self) -> int:
+        """This table's error bits since the last reset (check_err_flag: synchronises, raises
+        on RS_ERRBIT_RANGE)."""
+        return check_err_flag(self.err_flag)
+
     def oob_detected(self) -> bool:
-        """True if any lookup since the last reset saw an out-of-range id (synchronises)."""
-        return bool(self.err_flag.item() & L.RS_ERRBIT_OOB)
+        """True if any lookup since the last reset saw an out-of-range id (synchronises).
+        Raises on RS_ERRBIT_RANGE (check_errors)."""
+        return bool(self.check_errors() & L.RS_ERRBIT_OOB)
 
     def reset_oob(self):
         self.err_flag.zero_()

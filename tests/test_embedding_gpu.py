@@ -379,6 +379,45 @@ def test_sort_ids_lsd_slot_sentinels(rng):
     assert int(s.n_unique.item()) == nu_ref
 
 
+def test_sort_ids_slot_wider_than_declared_is_reported(rng):
+    """A slot of 2^25 + 5 rows sorted with max_slot_rows = 1000 (device offsets that disagree
+    with the host's bound): the slot-segmented sort raises RS_ERRBIT_RANGE and the host check
+    turns it into an error. The ids stay below 2^24 (both digits below 4096). With the true
+    max_slot_rows the LSD sort runs: sorted, no flag. Only ids are read: no table exists."""
+    from recommender_amd.embedding import check_err_flag
+
+    V, n = (1 << 25) + 5, 5000
+    so = torch.tensor([0, V], dtype=torch.int64, device=DEV)
+    ids = rng.integers(0, 1 << 24, n).astype(np.int64)
+    ids_t = torch.from_numpy(ids).to(DEV)
+    flag = torch.zeros(1, dtype=torch.int32, device=DEV)
+    SortedIds(ids_t, V, so, err_flag=flag, max_slot_rows=1000)
+    assert int(flag.item()) & L.RS_ERRBIT_RANGE == 4
+    with pytest.raises(RuntimeError, match="RS_ERRBIT_RANGE"):
+        check_err_flag(flag)
+    flag.zero_()
+    s = SortedIds(ids_t, V, so, err_flag=flag, max_slot_rows=V)
+    assert check_err_flag(flag) == 0
+    rows_ref, pos_ref, nu_ref = O.sort_ids(ids.reshape(-1, 1), V, np.array([0, V], np.int64))
+    np.testing.assert_array_equal(s.rows.cpu().numpy().view(np.uint32), rows_ref)
+    np.testing.assert_array_equal(s.pos.cpu().numpy(), pos_ref)
+    assert int(s.n_unique.item()) == nu_ref
+
+
+def test_embedding_oob_detected_raises_on_range_bit():
+    """Embedding.oob_detected() goes through the host check: RS_ERRBIT_RANGE raises for every
+    existing caller, RS_ERRBIT_OOB alone still reads as True, reset_oob() clears both."""
+    t = Embedding(8, 4, device=DEV)
+    assert t.oob_detected() is False
+    t.err_flag.fill_(L.RS_ERRBIT_OOB)
+    assert t.oob_detected() is True and t.check_errors() == L.RS_ERRBIT_OOB
+    t.err_flag.fill_(L.RS_ERRBIT_OOB | L.RS_ERRBIT_RANGE)
+    with pytest.raises(RuntimeError, match="max_slot_rows"):
+        t.oob_detected()
+    t.reset_oob()
+    assert t.oob_detected() is False
+
+
 def test_sort_ids_empty():
     s = SortedIds(torch.zeros(0, dtype=torch.int64, device=DEV), 10)
     assert s.n == 0 and int(s.n_unique.item()) == 0

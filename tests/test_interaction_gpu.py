@@ -110,6 +110,37 @@ def test_fm(F, D, rng):
     assert_close_rel(et.grad.cpu().numpy(), O.fm_bwd(e, g), RTOL, gscale, "fm bwd")
 
 
+def test_golden_interaction_on_gpu():
+    """The HIP dot-interaction (all four modes) and FM kernels, forward and backward, on
+    tests/golden/interaction.npz against its stored float64 results (the fixture
+    tests/test_oracle.py::test_golden_interaction holds the oracle to)."""
+    import os
+
+    f = np.load(os.path.join(os.path.dirname(__file__), "golden", "interaction.npz"))
+    x = f["x"]
+    for si in (0, 1):
+        for sg in (0, 1):
+            self_i, skip = bool(si), bool(sg)
+            xt = torch.from_numpy(x).to(DEV).requires_grad_(True)
+            out = dot_interaction(xt, self_i, skip)
+            ref = f[f"z_{si}{sg}"]
+            assert out.shape == ref.shape
+            assert_close_rel(out.detach().cpu().numpy(), ref, RTOL, _pair_scale(x, self_i, skip),
+                             f"fwd {si}{sg}")
+            g = f[f"g_{si}{sg}"]
+            out.backward(torch.from_numpy(g).to(DEV))
+            gscale = np.abs(g).max() * np.sqrt((x.astype(np.float64) ** 2).sum(-1)).max() * 2
+            assert_close_rel(xt.grad.cpu().numpy(), f[f"gx_{si}{sg}"], RTOL, gscale, f"bwd {si}{sg}")
+    e, g = f["fm_e"], f["fm_g"]
+    et = torch.from_numpy(e).to(DEV).requires_grad_(True)
+    out = fm_interaction(et)
+    assert_close_rel(out.detach().cpu().numpy(), f["fm_out"], RTOL, (np.abs(e).sum(1) ** 2).sum(-1),
+                     "fm fwd")
+    out.backward(torch.from_numpy(g).to(DEV))
+    gscale = np.abs(g)[:, None, None] * np.abs(e).sum(1, keepdims=True)
+    assert_close_rel(et.grad.cpu().numpy(), f["fm_ge"], RTOL, gscale, "fm bwd")
+
+
 def test_dlrm_model_compact_equals_reference_layout(rng):
     from recommender_amd.ctr.model import DLRM
 
