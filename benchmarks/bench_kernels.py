@@ -467,6 +467,41 @@ def dlrm_path(iters, out):
         report(name + " (alone)", cfg, us, kernel_bytes(name, B, S, D, 8, U), out)
     report("embedding_path (fwd + re-gathering bwd: 4 launches back to back, alone)",
            dict(cfg, bytes_per_example=round(per_ex, 1)), tot, per_ex * B, out)
+    apply_kinds(iters, out, table, s0, gemb, ws, cfg, U)
+
+
+def apply_kinds(iters, out, table, s0, gemb, ws, cfg, U, rounds=5):
+    """The sparse apply's three update rules — SGD (the yardstick), element-wise Adagrad and
+    row-wise Adagrad — over the same sorted ids and gradient rows, interleaved: `rounds` rounds of
+    SGD, Adagrad, row-wise, each timed over `iters` launches; the median round is reported with
+    every round's time next to it. lr 0, so the table stays put; the Adagrad accumulators grow by
+    g² per launch from 0.1 (no effect on the bytes moved). Bytes: the SGD apply's, plus the
+    accumulator read and written per touched row: 8·D bytes element-wise, 8 bytes row-wise."""
+    from bench import kernel_bytes
+
+    V, D = table.shape
+    n = s0.n
+    B, S = cfg["B"], cfg["S"]
+    st = L.stream_ptr(torch.device(DEV))
+    prm = L.AdamParams(0.0, 0.0, 0.0, 0.0, 0.0, 1e-7)
+    acc_el = torch.full((V, D), 0.1, device=DEV)
+    acc_row = torch.full((V,), 0.1, device=DEV)
+    base = kernel_bytes("rs_embedding_apply", B, S, D, 8, U)
+    kinds = (("sgd", L.RS_OPT_SGD, None, base),
+             ("adagrad", L.RS_OPT_ADAGRAD, acc_el, base + U * 8 * D),
+             ("rowwise_adagrad", L.RS_OPT_ROWWISE_ADAGRAD, acc_row, base + U * 8))
+    times = {k[0]: [] for k in kinds}
+    for _ in range(rounds):
+        for name, opt, acc, _ in kinds:
+            times[name].append(timed(lambda: L.call(
+                "rs_embedding_apply", opt, L.ptr(table), L.ptr(acc), None, V, D, L.ptr(s0.rows),
+                L.ptr(s0.pos), n, L.ptr(gemb), prm, None, L.ptr(ws), ws.numel(), st), iters))
+    sgd = float(np.median(times["sgd"]))
+    for name, _, _, nbytes in kinds:
+        us = float(np.median(times[name]))
+        report(f"rs_embedding_apply[{name}] (interleaved, median of {rounds})",
+               dict(cfg, rounds_us=[round(t, 1) for t in times[name]],
+                    ratio_to_sgd=round(us / sgd, 3)), us, nbytes, out)
 
 
 def sort_only(iters, out):

@@ -49,7 +49,19 @@ extern "C" {
 #define RS_OPT_SGD 0        /* var[u] -= lr * g_u                         (ctr/train.py:77-79) */
 #define RS_OPT_LAZY_ADAM 1  /* Adam on touched rows only                   (SURVEY §8a-2 b)   */
 #define RS_OPT_KERAS_ADAM 2 /* Keras OptimizerV2 Adam, dense decay of m/v/var (ctr/train.py:80) */
-#define RS_OPT_ADAGRAD 3    /* reserved */
+/* Adagrad on the touched rows (Keras Adagrad / TF ResourceSparseApplyAdagradV2 after
+ * deduplication), fp32, every operation rounded on its own; g = the row's segment sum. The
+ * accumulator is the m slot; v and the touched bitmap are ignored (may be NULL); lr and epsilon
+ * come from rs_adam_params, its other fields are ignored. Untouched rows and their accumulators
+ * are neither read nor written.
+ *   RS_OPT_ADAGRAD, m = [n_rows, dim], per element:
+ *     a = acc + g*g;  w -= (lr*g) / (sqrtf(a) + epsilon);  acc = a
+ *   RS_OPT_ROWWISE_ADAGRAD, m = [n_rows], per touched row r of width dim:
+ *     s = sum_d g[d]*g[d] (fp32; the order is fixed by the row geometry: same bits every run)
+ *     a = acc[r] + s / (float)dim;  w[d] -= (lr*g[d]) / (sqrtf(a) + epsilon) for every d;
+ *     acc[r] = a (one store per row) */
+#define RS_OPT_ADAGRAD 3
+#define RS_OPT_ROWWISE_ADAGRAD 4
 
 typedef struct rs_adam_params {
   float lr;        /* SGD: learning rate. Adam: lr_t = lr*sqrt(1-b2^t)/(1-b1^t), host-computed fp32 */
@@ -310,7 +322,8 @@ int32_t rs_keras_adam_flat(float* var, float* m, float* v, const float* grad, in
  * (Keras Adam _resource_apply_sparse / SGD _resource_apply_sparse_duplicate_indices,
  * [3p] reached from ctr/train.py:80,84,97 and the commented SGD path ctr/train.py:77-79).
  * Same summation order as rs_embedding_dedup_grad. m, v: optimizer slots [n_rows, dim]
- * (NULL for SGD). For RS_OPT_KERAS_ADAM call rs_keras_adam_dense_sweep afterwards with the
+ * (NULL for SGD; for the Adagrad kinds m is the accumulator — [n_rows, dim] or, row-wise,
+ * [n_rows] — and v is ignored: a NULL accumulator is RS_E_INVALID). For RS_OPT_KERAS_ADAM call rs_keras_adam_dense_sweep afterwards with the
  * same touched bitmap ([ceil(n_rows/32)] uint32, zero on entry): the pair reproduces Keras'
  * dense m/v decay and dense var update. */
 size_t rs_apply_workspace_size(int64_t n_ids, int32_t dim);
@@ -348,6 +361,13 @@ int32_t rs_apply_lazy_adam(float* table, float* m, float* v, int64_t n_rows, int
                            const int64_t* slot_offsets, int32_t n_slots, const float* grad_out,
                            const rs_adam_params* params, int32_t* err_flag, void* workspace,
                            size_t ws_bytes, void* stream);
+/* Adagrad (rowwise = 0: RS_OPT_ADAGRAD, accum [n_rows, dim]; else RS_OPT_ROWWISE_ADAGRAD, accum
+ * [n_rows]): rs_sort_ids + rs_embedding_apply, bit-identical to the two calls. */
+int32_t rs_apply_adagrad(float* table, float* accum, int64_t n_rows, int32_t dim, const void* ids,
+                         int32_t id_dtype, int64_t n_ids, const int64_t* slot_offsets,
+                         int32_t n_slots, const float* grad_out, float lr, float epsilon,
+                         int32_t rowwise, int32_t* err_flag, void* workspace, size_t ws_bytes,
+                         void* stream);
 int32_t rs_apply_keras_dense_adam(float* table, float* m, float* v, int64_t n_rows, int32_t dim,
                                   const void* ids, int32_t id_dtype, int64_t n_ids,
                                   const int64_t* slot_offsets, int32_t n_slots,

@@ -21,6 +21,8 @@ RS_ID_I64 = 1
 RS_OPT_SGD = 0
 RS_OPT_LAZY_ADAM = 1
 RS_OPT_KERAS_ADAM = 2
+RS_OPT_ADAGRAD = 3
+RS_OPT_ROWWISE_ADAGRAD = 4
 RS_DEDUP_TILE = 32
 RS_ERRBIT_OOB = 1
 RS_ERRBIT_FORMAT = 2
@@ -250,6 +252,8 @@ _SIGS = {
                             _p]),
     "rs_apply_lazy_adam": (_i32, [_p, _p, _p, _i64, _i32, _p, _i32, _i64, _p, _i32, _p,
                                   C.POINTER(AdamParams), _p, _p, _sz, _p]),
+    "rs_apply_adagrad": (_i32, [_p, _p, _i64, _i32, _p, _i32, _i64, _p, _i32, _p, C.c_float,
+                                C.c_float, _i32, _p, _p, _sz, _p]),
     "rs_apply_keras_dense_adam": (_i32, [_p, _p, _p, _i64, _i32, _p, _i32, _i64, _p, _i32, _p,
                                          C.POINTER(AdamParams), _p, _p, _p, _sz, _p]),
     "rs_vocab_count_masked": (_i32, [_p, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p]),

@@ -166,12 +166,13 @@ __global__ __launch_bounds__(256) void gather_flat2_kernel(const float* __restri
 // ---- a-2: segmented sum + apply -------------------------------------------------------
 // OPT_EMIT: segment sums to (uniq_rows, uniq_grad) in segment order; OPT_DENSE: each segment sum
 // stored as row `row` of a dense [n_rows, dim] gradient (a.table)
-enum { OPT_SGD = RS_OPT_SGD, OPT_LAZY = RS_OPT_LAZY_ADAM, OPT_KERAS = RS_OPT_KERAS_ADAM, OPT_EMIT = 100,
+enum { OPT_SGD = RS_OPT_SGD, OPT_LAZY = RS_OPT_LAZY_ADAM, OPT_KERAS = RS_OPT_KERAS_ADAM,
+       OPT_ADAGRAD = RS_OPT_ADAGRAD, OPT_ROWWISE = RS_OPT_ROWWISE_ADAGRAD, OPT_EMIT = 100,
        OPT_DENSE = 101 };
 
 struct ApplyArgs {
   float* table;
-  float* m;
+  float* m;  // Adam m; Adagrad accumulator ([n_rows, dim] element-wise, [n_rows] row-wise)
   float* v;
   int dim;
   rs_adam_params p;
@@ -240,6 +241,20 @@ __device__ __forceinline__ void finalize_chunk(const ApplyArgs& a, uint32_t row,
 #pragma unroll
     for (int e = 0; e < VEC; ++e) w[e] = w[e] - a.p.lr * g[e];
     RowIO<VEC>::store(t, w);
+  } else if constexpr (OPT == OPT_ADAGRAD) {  // Keras / TF ResourceSparseApplyAdagradV2 op order
+    int64_t off = (int64_t)row * a.dim + col;
+    float w[VEC], h[VEC];
+    RowIO<VEC>::load(a.table + off, w);
+    RowIO<VEC>::load(a.m + off, h);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      float hh = h[e] + g[e] * g[e];
+      float upd = (a.p.lr * g[e]) / (sqrtf(hh) + a.p.epsilon);
+      h[e] = hh;
+      w[e] = w[e] - upd;
+    }
+    RowIO<VEC>::store(a.table + off, w);
+    RowIO<VEC>::store(a.m + off, h);
   } else {  // lazy / keras Adam on a touched row (Keras _resource_apply_sparse op order)
     int64_t off = (int64_t)row * a.dim + col;
     float w[VEC], m[VEC], v[VEC];
@@ -267,10 +282,49 @@ __device__ __forceinline__ void finalize_chunk(const ApplyArgs& a, uint32_t row,
 template <int OPT, int VEC, int CPL>
 __device__ __forceinline__ void finalize_row(const ApplyArgs& a, uint32_t row, int gl, int lpr,
                                              const float (&acc)[CPL][VEC], int32_t seg_id) {
+  if constexpr (OPT == OPT_ROWWISE) {
+    // Row-wise Adagrad: one accumulator per row, so the row's sum of squares comes first. Each
+    // lane sums its own elements (lanes and chunks past dim hold loaded-but-unused values: they
+    // are masked), then an xor butterfly over the row's lpr lanes leaves every lane the same
+    // bits (fp32 add commutes, so both sides of each exchange form the same sum). Every call
+    // site reaches this with all lpr lanes of the row's group active and on the same row (the
+    // walks branch on keys the whole group shares; the fix-ups select whole groups); other
+    // groups of the wave may be elsewhere, and the exchange never leaves the group.
+    // The accumulator and the table row are requested first: they fly under the reduction.
+    const float h0 = a.m[row];
+    float w[CPL][VEC];
 #pragma unroll
-  for (int c = 0; c < CPL; ++c) {
-    int col = (gl + c * lpr) * VEC;
-    if (col < a.dim) finalize_chunk<OPT, VEC>(a, row, col, acc[c], seg_id);
+    for (int c = 0; c < CPL; ++c) {
+      int col = (gl + c * lpr) * VEC;
+      if (col < a.dim) RowIO<VEC>::load(a.table + (int64_t)row * a.dim + col, w[c]);
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const bool in = (gl + c * lpr) * VEC < a.dim;
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) s += in ? acc[c][e] * acc[c][e] : 0.f;
+    }
+    for (int off = lpr >> 1; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    const float h = h0 + s / (float)a.dim;
+    const float den = sqrtf(h) + a.p.epsilon;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      int col = (gl + c * lpr) * VEC;
+      if (col < a.dim) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) w[c][e] = w[c][e] - (a.p.lr * acc[c][e]) / den;
+        RowIO<VEC>::store(a.table + (int64_t)row * a.dim + col, w[c]);
+      }
+    }
+    // one store per row; every lane of the row took h0 from the one load instruction above
+    if (gl == 0) a.m[row] = h;
+  } else {
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      int col = (gl + c * lpr) * VEC;
+      if (col < a.dim) finalize_chunk<OPT, VEC>(a, row, col, acc[c], seg_id);
+    }
   }
   // (Keras' touched-row bitmap is marked by keras_bitmap_mark_kernel after the walk: an atomic
   // here, inlined into every emit of the unrolled walk, took the Keras walk past 128 VGPRs —
@@ -1138,6 +1192,12 @@ __global__ __launch_bounds__(256) void keras_bitmap_mark_kernel(const uint32_t* 
 // The D = 128 SGD walk queues its table updates 2 runs at a time (tile32_walk<OPT_SGD, 2>; Q = 3
 // and 4 spill at 128 VGPRs): round 4's A/B against the one-run-at-a-time walk, 200 steps each,
 // interleaved: step 0.685-0.688 -> 0.671-0.674 ms, apply alone 238 -> 230 us, bit-identical.
+// The Adam and Adagrad kinds walk one run at a time: queued two at a time, the row-wise Adagrad
+// walk needs 40 bytes of scratch per lane at the kernel's 128-VGPR limit (sparse
+// Adagrad). RS_SGD_QUEUE=0 (A/B builds) gives SGD that walk too, the yardstick for their cost.
+#ifndef RS_SGD_QUEUE
+#define RS_SGD_QUEUE 2
+#endif
 
 static int32_t launch_segments(int opt, const uint32_t* keys, const int32_t* pos, int64_t n,
                                int64_t n_rows, const float* grad, const ApplyArgs& a,
@@ -1172,7 +1232,7 @@ static int32_t launch_segments(int opt, const uint32_t* keys, const int32_t* pos
   RS_DISPATCH_VEC_CPL(geom, ({                                                                  \
     if (g32) {                                                                                  \
       if (OPTV == OPT_SGD)                                                                      \
-        seg_group32_kernel<OPTV, 2><<<ceil_div(n_tiles, 32), 1024, 0, st>>>(                    \
+        seg_group32_kernel<OPTV, RS_SGD_QUEUE><<<ceil_div(n_tiles, 32), 1024, 0, st>>>(         \
             keys, pos, n, (uint32_t)n_rows, grad, a, n_tiles);                                  \
       else                                                                                      \
         seg_group32_kernel<OPTV><<<ceil_div(n_tiles, 32), 1024, 0, st>>>(keys, pos, n,          \
@@ -1198,6 +1258,8 @@ static int32_t launch_segments(int opt, const uint32_t* keys, const int32_t* pos
   switch (opt) {
     case OPT_SGD: RS_SEG_LAUNCH(OPT_SGD); break;
     case OPT_LAZY: RS_SEG_LAUNCH(OPT_LAZY); break;
+    case OPT_ADAGRAD: RS_SEG_LAUNCH(OPT_ADAGRAD); break;
+    case OPT_ROWWISE: RS_SEG_LAUNCH(OPT_ROWWISE); break;
     case OPT_KERAS:
       RS_SEG_LAUNCH(OPT_KERAS);
       keras_bitmap_mark_kernel<<<(unsigned)std::min<int64_t>(ceil_div(n, 256), 2048), 256, 0, st>>>(
@@ -1491,9 +1553,11 @@ extern "C" int32_t rs_embedding_apply_scaled(int32_t opt, float* table, float* m
   RS_CHECK_ARG(dim > 0 && n_ids >= 0 && n_rows > 0, "bad sizes");
   RS_CHECK_ARG(!row_scale || scale_group >= 1, "scale_group must be >= 1");
   RS_CHECK_ARG(params, "params is null");
-  RS_CHECK_ARG(opt == RS_OPT_SGD || opt == RS_OPT_LAZY_ADAM || opt == RS_OPT_KERAS_ADAM,
+  const bool adagrad = opt == RS_OPT_ADAGRAD || opt == RS_OPT_ROWWISE_ADAGRAD;
+  RS_CHECK_ARG(opt == RS_OPT_SGD || opt == RS_OPT_LAZY_ADAM || opt == RS_OPT_KERAS_ADAM || adagrad,
                "unknown optimizer %d", opt);
-  RS_CHECK_ARG(opt == RS_OPT_SGD || (m && v), "Adam needs m and v slots");
+  RS_CHECK_ARG(!adagrad || m, "Adagrad needs its accumulator (the m slot): accumulator is null");
+  RS_CHECK_ARG(opt == RS_OPT_SGD || adagrad || (m && v), "Adam needs m and v slots");
   RS_CHECK_ARG(opt != RS_OPT_KERAS_ADAM || touched_bitmap, "Keras Adam needs the touched bitmap");
   if (n_ids == 0) return RS_OK;
   RS_CHECK_ARG(table && sorted_rows && sorted_pos && grad_out, "null pointer");
@@ -1504,16 +1568,18 @@ extern "C" int32_t rs_embedding_apply_scaled(int32_t opt, float* table, float* m
   ApplyArgs a{};
   a.table = table;
   a.m = m;
-  a.v = v;
+  a.v = adagrad ? nullptr : v;
   a.dim = dim;
   a.p = *params;
-  a.bitmap = touched_bitmap;
+  a.bitmap = adagrad ? nullptr : touched_bitmap;
   a.row_scale = row_scale;
   a.scale_group = scale_group;
   a.partial = static_cast<float*>(workspace);
   a.chunk = chunk_of(a.partial, n_ids, dim);
   a.tile_flags = flags_of(a.partial, n_ids, dim);
-  const void* ptrs[4] = {table, grad_out, m ? m : table, v ? v : table};
+  // the row-wise accumulator is one float per row, never moved as a vector; Adagrad ignores v
+  const void* ptrs[4] = {table, grad_out, m && opt != RS_OPT_ROWWISE_ADAGRAD ? m : table,
+                         v && !adagrad ? v : table};
   RowGeom geom = row_geom(dim, ptrs, 4);
   return launch_segments(opt, sorted_rows, sorted_pos, n_ids, n_rows, grad_out, a, geom,
                          as_stream(stream));

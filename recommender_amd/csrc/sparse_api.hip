@@ -2,6 +2,7 @@
 //   rs_embedding_bwd_dedup   ids + grad rows -> (unique rows, summed grads, count)
 //   rs_apply_sgd             var[u] -= lr * Σ g  (SGD _resource_apply_sparse_duplicate_indices)
 //   rs_apply_lazy_adam       Keras Adam on the touched rows only
+//   rs_apply_adagrad         Adagrad on the touched rows, element-wise or row-wise accumulator
 //   rs_apply_keras_dense_adam  exact Keras Adam (touched-row update + dense m/v decay sweep)
 // Each is rs_sort_ids followed by rs_embedding_dedup_grad / rs_embedding_apply (and
 // rs_keras_adam_dense_sweep) with one caller workspace (rs_sparse_workspace_size): the same
@@ -106,6 +107,19 @@ extern "C" int32_t rs_apply_lazy_adam(float* table, float* m, float* v, int64_t 
   return apply_common(RS_OPT_LAZY_ADAM, table, m, v, n_rows, dim, ids, id_dtype, n_ids,
                       slot_offsets, n_slots, grad_out, params, nullptr, err_flag, workspace,
                       ws_bytes, stream);
+}
+
+extern "C" int32_t rs_apply_adagrad(float* table, float* accum, int64_t n_rows, int32_t dim,
+                                    const void* ids, int32_t id_dtype, int64_t n_ids,
+                                    const int64_t* slot_offsets, int32_t n_slots,
+                                    const float* grad_out, float lr, float epsilon,
+                                    int32_t rowwise, int32_t* err_flag, void* workspace,
+                                    size_t ws_bytes, void* stream) {
+  RS_CHECK_ARG(accum, "rs_apply_adagrad: the accumulator is required");
+  rs_adam_params p{lr, 0.f, 0.f, 0.f, 0.f, epsilon};
+  return apply_common(rowwise ? RS_OPT_ROWWISE_ADAGRAD : RS_OPT_ADAGRAD, table, accum, nullptr,
+                      n_rows, dim, ids, id_dtype, n_ids, slot_offsets, n_slots, grad_out, &p,
+                      nullptr, err_flag, workspace, ws_bytes, stream);
 }
 
 extern "C" int32_t rs_apply_keras_dense_adam(float* table, float* m, float* v, int64_t n_rows,

@@ -6,6 +6,8 @@ Same flags and defaults as the reference (--gpus, --gpu_memory_limit, --model_ty
 dim 16, 3 epochs, DLRM units [512,256,64,16] / [512,256,1], Adam) plus:
   --optimizer  keras_adam (reference default, ctr/train.py:80,84) | lazy_adam | sgd
                (the commented DLRM SGD + DLRMScheduler path, ctr/train.py:77-79)
+               | adagrad | rowwise_adagrad (Keras Adagrad defaults; the tables' accumulator
+               per element or one per row, optim.SparseAdagrad)
   --steps_per_epoch, --rows/--slab (per-slot tables), --embedding_size.
 Loss: BinaryCrossentropy(reduction=NONE) (ctr/train.py:85) still calls
 keras.losses.binary_crossentropy, which averages over the LAST axis [3p TF 2.2]; the models
@@ -26,7 +28,7 @@ from .. import _lib as L
 from ..functional import binary_crossentropy
 from ..nn import invalidate_compose_cache, overlapped_param_grads, overlapped_weight_grads
 from ..metrics import AUC
-from ..optim import DLRMScheduler, KerasAdam, SparseAdam, SparseSGD
+from ..optim import DLRMScheduler, KerasAdam, SparseAdagrad, SparseAdam, SparseSGD
 from ..synthetic import criteo_batch, criteo_cardinalities
 from .model import DLRM, DeepFM
 
@@ -82,6 +84,19 @@ class TrainStep:
             self.opt_sparse = SparseAdam(tables, lr=lr, mode="keras" if optimizer == "keras_adam" else "lazy",
                                          fused=fused, defer_join=defer_sparse_join,
                                          defer_decay=defer_decay and optimizer == "keras_adam")
+            self._sched = None
+        elif optimizer in ("adagrad", "rowwise_adagrad"):
+            if self.sharded:
+                # the owner-side apply has its own ordering and oracle (oracle/sharded.py)
+                raise ValueError("the row-sharded slab does not support Adagrad yet "
+                                 f"(optimizer={optimizer!r}); use sgd")
+            lr = lr if lr is not None else 1e-3
+            # Keras Adagrad defaults on both sides; the dense Adagrad is not the tail kernel's
+            # plain SGD, so the fused step calls opt_dense.step() (dense_tail_ready is false)
+            self.opt_dense = torch.optim.Adagrad(dense, lr=lr, initial_accumulator_value=0.1,
+                                                 eps=1e-7)
+            self.opt_sparse = SparseAdagrad(tables, lr=lr, rowwise=optimizer == "rowwise_adagrad",
+                                            fused=fused, defer_join=defer_sparse_join)
             self._sched = None
         else:
             raise ValueError(f"unknown optimizer {optimizer}")
@@ -360,7 +375,7 @@ def train(argv=None):
     ap.add_argument("--train_batch_size", type=int, default=1024)
     ap.add_argument("--test_batch_size", type=int, default=4096)
     ap.add_argument("--seed", type=int, default=4)
-    ap.add_argument("--optimizer", default="keras_adam", choices=["keras_adam", "lazy_adam", "sgd"])
+    ap.add_argument("--optimizer", default="keras_adam", choices=["keras_adam", "lazy_adam", "sgd", "adagrad", "rowwise_adagrad"])
     ap.add_argument("--loss_reduction", default="mean", choices=["sum", "mean"])
     ap.add_argument("--embedding_size", type=int, default=16)
     ap.add_argument("--vocab_size", type=int, default=1_000_000)

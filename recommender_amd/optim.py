@@ -6,6 +6,8 @@ Embedding (a-2):
   SparseAdam(lazy) Adam on touched rows only     (roofline mode)
   SparseAdam(keras) Keras OptimizerV2 Adam exactly: dense decay of m/v and dense var update of
                    every row (ctr/train.py:80,84 `tf.keras.optimizers.Adam()` defaults)
+  SparseAdagrad    Keras Adagrad on touched rows: acc += g², var -= lr·g/(√acc + ε); rowwise=True
+                   keeps one accumulator per row (acc[r] += mean g²: 4 bytes of state per row)
 Dense:
   KerasAdam        Keras Adam update rule on torch tensors (lr_t folding, eps outside sqrt)
   DLRMScheduler    warmup-linear then cosine decay (ctr/util.py:7-37)
@@ -414,6 +416,39 @@ class SparseAdam(SparseOptimizer):
         lr = self.lr(self.iterations) if callable(self.lr) else self.lr
         return keras_adam_coefficients(self.iterations + 1, lr, self.beta_1, self.beta_2,
                                        self.epsilon)
+
+
+class SparseAdagrad(SparseOptimizer):
+    """Keras Adagrad on the touched rows (TF ResourceSparseApplyAdagradV2 after deduplication):
+    a = acc + g²; var -= lr·g / (√a + ε); acc = a, with g the row's segment sum.
+
+    rowwise=True keeps one accumulator per row instead of one per element: a = acc[r] +
+    mean_d(g[d]²), the same a for every element of the row — 4 bytes of state per row where the
+    element-wise form holds a slot of table size. state[id(table)] is the accumulator:
+    [input_dim, dim] fp32, or [input_dim] row-wise. lr may be a float or a schedule step → lr.
+    Untouched rows and their accumulators are neither read nor written."""
+
+    def __init__(self, tables, lr=1e-3, initial_accumulator_value=0.1, epsilon=1e-7,
+                 rowwise=False, fused=False, defer_join=False):
+        super().__init__(tables, lr, fused=fused, defer_join=defer_join)
+        self.epsilon = epsilon
+        self.initial_accumulator_value = initial_accumulator_value
+        self.rowwise = bool(rowwise)
+        self.kind = L.RS_OPT_ROWWISE_ADAGRAD if self.rowwise else L.RS_OPT_ADAGRAD
+        self.state = {}
+        for t in self.tables:
+            w = t.weight
+            shape = (t.input_dim,) if self.rowwise else tuple(w.shape)
+            self.state[id(t)] = torch.full(shape, float(initial_accumulator_value),
+                                           dtype=torch.float32, device=w.device)
+
+    def _params(self) -> L.AdamParams:
+        lr = self.lr(self.iterations) if callable(self.lr) else self.lr
+        return L.AdamParams(float(np.float32(lr)), 0.0, 0.0, 0.0, 0.0,
+                            float(np.float32(self.epsilon)))
+
+    def _slots(self, t):
+        return self.state[id(t)], None, None
 
 
 class KerasAdam(torch.optim.Optimizer):
