@@ -148,11 +148,13 @@ def dien_encode(text: str, items: dict, cats: dict, maxlen: int):
             np.array(lab, np.float32).reshape(n, 1))
 
 
-def dien_cat_of_item(items: dict, cats: dict, i2c: dict) -> np.ndarray:
+def dien_cat_of_item(items: dict, cats: dict, i2c: dict, missing=None) -> np.ndarray:
     """cat id of every item id 0..n_items+1 (0 for the mask id): the map the negative sampler
-    reads (index_cat_id(item_id2cat_id[reverse_vocab[idx]]), data_loader.py:54)."""
+    reads (index_cat_id(item_id2cat_id[reverse_vocab[idx]]), data_loader.py:54). An item that
+    never had a cat partner (a history with more items than cats: zip drops it) is not in
+    item_id2cat_id: KeyError as in the reference, or `missing` in its place when given."""
     out = np.zeros(len(items), np.int32)
     for it, idx in items.items():
         if it != "mask":
-            out[idx] = cats[i2c[it]]
+            out[idx] = cats[i2c[it]] if missing is None or it in i2c else missing
     return out

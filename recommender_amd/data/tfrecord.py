@@ -52,7 +52,10 @@ def index_records(data: np.ndarray, verify_crc: bool = True):
 def read_tfrecord(src, device="cuda", verify_crc: bool = True, n_int: int = NUM_INT,
                   n_cat: int = NUM_CAT):
     """({'int_features', 'cat_features'}, label) of every record, on the device. Raises on
-    corrupt framing; a malformed Example raises after the parse (its row is zeroed)."""
+    corrupt framing; a malformed Example raises after the parse (its row is zeroed). One
+    Example may be at most 4,096 bytes (kRecMax in csrc/tfrecord.hip: a wave stages its record in
+    LDS); a longer payload counts as malformed and raises ValueError, whatever it holds. The
+    reference's records are a few hundred bytes."""
     dev = torch.device(device)
     host = _host_bytes(src)
     offs, lens = index_records(host, verify_crc)
