@@ -12,6 +12,7 @@ constexpr int kLossMaxBlocks = 1024;
 
 __device__ __forceinline__ float bce_term(float p, float y, float eps) {
   float pc = fminf(fmaxf(p, eps), 1.f - eps);
+  pc = p != p ? p : pc;  // fminf / fmaxf drop a NaN: keep it, as clip_by_value does
   float a = y * logf(pc + eps);
   float b = (1.f - y) * logf((1.f - pc) + eps);
   return -(a + b);
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(kLossThreads) void bce_bwd_kernel(const float* __re
     const bool inside = pi >= eps && pi <= 1.f - eps;  // clip_by_value passes the gradient inside
     const float pc = fminf(fmaxf(pi, eps), 1.f - eps);
     const float d = -(yi / (pc + eps)) + (1.f - yi) / ((1.f - pc) + eps);
-    dp[i] = inside ? g * d : 0.f;
+    dp[i] = inside ? g * d : (pi != pi ? pi : 0.f);  // a NaN prediction has a NaN gradient
   }
 }
 
