@@ -194,7 +194,7 @@ class TrainStep:
         sparse Adam decays m / v and moves every row each step anyway, so this dense step is the
         same update as __call__'s sparse apply + dense sweep (tests/test_deepfm_gpu.py: bit for
         bit). Its Adam state is its own: do not interleave with __call__."""
-        from ..optim import GraphKerasAdam, _Workspace, densify_grad
+        from ..optim import GraphKerasAdam, densify_grad
 
         if (not isinstance(self.opt_sparse, SparseAdam) or self.opt_sparse.kind != L.RS_OPT_KERAS_ADAM
                 or self.opt_sparse.fused or self.sharded):
@@ -205,7 +205,7 @@ class TrainStep:
             self._gdense = [p for p in self.dense if id(p) not in tw and p.numel() > 0]
             self.opt_graph = GraphKerasAdam(self._gdense + [t.weight for t in tables],
                                             lr=self.opt_dense.param_groups[0]["lr"])
-            self._gws = _Workspace()
+            self._gws = L.Workspace()
             self.opt_sparse.release_state()  # the graph path's Adam state is opt_graph's
         for p in self._gdense:
             p.grad = None

@@ -35,18 +35,6 @@ def _mask_u8(mask, shape, device):
 # (csrc/dien_proj.hip): a masked step carries the state, so its input projection is never read
 # and its gradient rows are exactly 0 — the library GEMMs over all B·L rows spent ≈1 ms of the
 # cfg3 step on them. Widths beyond the kernels' (input > 64) keep the GEMMs.
-_proj_ws: dict = {}
-
-
-def _ws(name, nbytes, dev):
-    key = (name, dev)
-    b = _proj_ws.get(key)
-    if b is None or b.numel() < nbytes:
-        b = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-        _proj_ws[key] = b
-    return b
-
-
 def _rows_ready(X, H):
     return X <= 64 and H <= 64
 
@@ -69,7 +57,7 @@ def _valid_rows_list(mask_u8):
     idx = torch.empty(R, dtype=torch.int32, device=dev)
     cnt = torch.empty(1, dtype=torch.int32, device=dev)
     nb = L.lib().rs_valid_rows_workspace_size(R)
-    ws = _ws("valid_rows", nb, dev)
+    ws = L.workspace("dien.valid_rows", nb, dev)
     L.call("rs_valid_rows", L.ptr(mask_u8), R, L.ptr(idx), L.ptr(cnt), L.ptr(ws), ws.numel(),
            L.stream_ptr(dev))
     return idx, cnt
@@ -110,7 +98,7 @@ def _masked_wgrad(A2, shift_L, D2, vr, sums=True):
     C = torch.empty(K, N, device=dev)
     s = torch.empty(N, device=dev) if sums else None
     nb = L.lib().rs_masked_wgrad_workspace_size(K, N)
-    ws = _ws("masked_wgrad", nb, dev)
+    ws = L.workspace("dien.masked_wgrad", nb, dev)
     L.call("rs_masked_wgrad", L.ptr(A2), _ld(A2), shift_L, L.ptr(D2), _ld(D2), L.ptr(vr[0]),
            L.ptr(vr[1]), K, N, L.ptr(C), L.ptr(s), L.ptr(ws), ws.numel(), L.stream_ptr(dev))
     return C, s
@@ -457,7 +445,7 @@ class _BatchNormFn(torch.autograd.Function):
         y = torch.empty_like(x)
         mean = torch.empty(C, device=dev)
         invstd = torch.empty(C, device=dev)
-        ws = _ws("batch_norm", L.lib().rs_batch_norm_workspace_size(B, C), dev)
+        ws = L.workspace("dien.batch_norm", L.lib().rs_batch_norm_workspace_size(B, C), dev)
         L.call("rs_batch_norm_fwd", L.ptr(x), B, C, L.ptr(gamma), L.ptr(beta), bn.epsilon,
                bn.momentum, int(training), L.ptr(bn.moving_mean), L.ptr(bn.moving_variance),
                L.ptr(y), L.ptr(mean), L.ptr(invstd), L.ptr(ws), ws.numel(), L.stream_ptr(dev))
@@ -474,7 +462,7 @@ class _BatchNormFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         dgamma = torch.empty(C, device=dev)
         dbeta = torch.empty(C, device=dev)
-        ws = _ws("batch_norm_bwd", L.lib().rs_batch_norm_workspace_size(B, C), dev)
+        ws = L.workspace("dien.batch_norm_bwd", L.lib().rs_batch_norm_workspace_size(B, C), dev)
         L.call("rs_batch_norm_bwd", L.ptr(dy), L.ptr(x), B, C, L.ptr(mean), L.ptr(invstd),
                L.ptr(gamma), int(ctx.training), L.ptr(dx), L.ptr(dgamma), L.ptr(dbeta), L.ptr(ws),
                ws.numel(), L.stream_ptr(dev))

@@ -12,9 +12,10 @@ import time
 import numpy as np
 import torch
 
+from .._lib import Workspace
 from ..functional import binary_crossentropy
 from ..metrics import AUC
-from ..optim import GraphKerasAdam, KerasAdam, SparseAdam, _Workspace, densify_grad
+from ..optim import GraphKerasAdam, KerasAdam, SparseAdam, densify_grad
 from . import DIEN, DIN, BaseModel
 
 
@@ -82,7 +83,7 @@ class DIENStep:
                             if id(p) not in tw and p.numel() > 0]
             self.opt_graph = GraphKerasAdam(self._gdense + [t.weight for t in tables],
                                             lr=self.opt_dense.param_groups[0]["lr"])
-            self._ws = _Workspace()
+            self._ws = Workspace()
             self.opt_sparse.release_state()  # the graph path's Adam state is opt_graph's
         for p in self._gdense:
             p.grad = None

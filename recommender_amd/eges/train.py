@@ -15,7 +15,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ..optim import GraphKerasAdam, SparseAdam, _Workspace, densify_grad
+from .._lib import Workspace
+from ..optim import GraphKerasAdam, SparseAdam, densify_grad
 from .model import EGES, GES, DeepWalk
 from .sampler import EGESPairSampler
 
@@ -79,7 +80,7 @@ class EGESStep:
         tables = self.model.tables()
         if getattr(self, "opt_graph", None) is None:
             self.opt_graph = GraphKerasAdam([t.weight for t in tables], lr=self.opt.lr)
-            self._ws = _Workspace()
+            self._ws = Workspace()
             self.opt.release_state()  # the graph path's Adam state is opt_graph's
         logits = self.model(inputs)
         loss = F.binary_cross_entropy_with_logits(logits, labels)

@@ -80,10 +80,9 @@ class _ExpertsGatesFn(torch.autograd.Function):
         dz2 = torch.empty_like(y2)
         db1 = torch.empty(E, 1, H1, device=dev)
         if B % 512 == 0:
-            ws = torch.empty(max(1, L.lib().rs_act_bwd_colsum_workspace_size(E * B, H1) // 4),
-                             device=dev)
+            ws = L.scratch(L.lib().rs_act_bwd_colsum_workspace_size(E * B, H1), dev)
             L.call("rs_act_bwd_colsum_groups", L.ptr(dy2), L.ptr(y2), E * B, H1, 1, E, L.ptr(dz2),
-                   L.ptr(db1), L.ptr(ws), ws.numel() * 4, st)
+                   L.ptr(db1), L.ptr(ws), ws.numel(), st)
         else:
             for e in range(E):
                 _act_bwd(dy2[e], y2[e], 1, True, dz=dz2[e], db=db1[e, 0])

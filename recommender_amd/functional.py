@@ -360,9 +360,9 @@ class _BCE(torch.autograd.Function):
         n = p.numel()
         red = _RED[reduction]
         out = torch.empty(p.shape if red == 0 else (), device=p.device, dtype=torch.float32)
-        ws = torch.empty(max(1, L.lib().rs_bce_workspace_size(n) // 4), device=p.device)
+        ws = L.scratch(L.lib().rs_bce_workspace_size(n), p.device)
         L.call("rs_bce_fwd", L.ptr(p), L.ptr(y), n, eps, red, L.ptr(out), L.ptr(ws),
-               ws.numel() * 4, L.stream_ptr(p.device))
+               ws.numel(), L.stream_ptr(p.device))
         ctx.save_for_backward(p, y)
         ctx.red, ctx.eps = red, eps
         return out
@@ -566,7 +566,8 @@ def _dense_tail_sgd(tl, rows, bl, A_top, s_top, P_bot, lr):
     comp3n = torch.empty(m + 1, b3, device=dev)
     q = torch.empty(width, device=dev)
     c = torch.empty(1, device=dev)
-    ws = _tail_ws(width, n1, n2, dev)
+    ws = L.workspace("dlrm.dense_tail", L.lib().rs_dlrm_dense_tail_workspace_size(width, n1, n2),
+                     dev)
     a = L.DlrmTailArgs()
     for i in range(3):
         a.top_k[i], a.top_b[i] = tl[i].kernel.data_ptr(), tl[i].bias.data_ptr()
@@ -582,7 +583,7 @@ def _dense_tail_sgd(tl, rows, bl, A_top, s_top, P_bot, lr):
     a.bot_dk2, a.bot_dk3, a.bot_P2, a.bot_P1 = dk2.data_ptr(), dk3.data_ptr(), P2.data_ptr(), P1.data_ptr()
     a.bot_comp2_next, a.bot_comp3_next = comp2n.data_ptr(), comp3n.data_ptr()
     a.lr = float(lr)
-    L.call("rs_dlrm_dense_tail", C.byref(a), L.ptr(ws), ws.numel() * 4, L.stream_ptr(dev))
+    L.call("rs_dlrm_dense_tail", C.byref(a), L.ptr(ws), ws.numel(), L.stream_ptr(dev))
     grads = list(zip(tdk, tdb)) + [(P1[:m], P1[m]), (dk2, P2[m]), (dk3, P_bot[m])]
     for layer, (dk, db) in zip(tl + bl, grads):
         layer.kernel.grad, layer.bias.grad = dk, db
@@ -594,27 +595,9 @@ def _dense_tail_sgd(tl, rows, bl, A_top, s_top, P_bot, lr):
     store_composed(bl, [comp2n, comp3n], tl, rows, width, (q, c))
 
 
-_tail_ws_cache: dict = {}
-
-
-def _tail_ws(n0, n1, n2, dev):
-    n = (L.lib().rs_dlrm_dense_tail_workspace_size(n0, n1, n2) + 3) // 4
-    t = _tail_ws_cache.get(dev)
-    if t is None or t.numel() < n:
-        t = torch.empty(n, device=dev)
-        _tail_ws_cache[dev] = t
-    return t
-
-
-_train_ws_cache: dict = {}
 _APPLY_EARLY = os.environ.get("RS_APPLY_EARLY", "1") == "1"
 
 
-
 def _train_ws(B, dev):
-    nb = L.lib().rs_dlrm_train_workspace_size(B)
-    t = _train_ws_cache.get(dev)
-    if t is None or t.numel() < nb:
-        t = torch.empty(nb, dtype=torch.uint8, device=dev)
-        _train_ws_cache[dev] = t
-    return t
+    """The train kernel's cached workspace (its per-block partial sums stay there after a step)."""
+    return L.workspace("dlrm.train", L.lib().rs_dlrm_train_workspace_size(B), dev)

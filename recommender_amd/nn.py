@@ -149,9 +149,9 @@ def _act_bwd(g, y, act, want_db, dz=None, db=None):
     R, N = g.shape
     dz = torch.empty_like(g) if dz is None else dz
     db = torch.empty(N, device=g.device, dtype=torch.float32) if db is None else db
-    ws = torch.empty(max(1, L.lib().rs_act_bwd_colsum_workspace_size(R, N) // 4), device=g.device)
+    ws = L.scratch(L.lib().rs_act_bwd_colsum_workspace_size(R, N), g.device)
     L.call("rs_act_bwd_colsum", L.ptr(g), L.ptr(y), R, N, act, L.ptr(dz), L.ptr(db), L.ptr(ws),
-           ws.numel() * 4, L.stream_ptr(g.device))
+           ws.numel(), L.stream_ptr(g.device))
     return dz, (db if want_db else None)
 
 
@@ -293,10 +293,9 @@ class _DenseFn(torch.autograd.Function):
         if act or layer.bias is not None:
             dz = torch.empty_like(dy) if act else dy
             db = torch.empty(fo, device=dy.device, dtype=torch.float32)
-            ws = torch.empty(max(1, L.lib().rs_act_bwd_colsum_workspace_size(B, fo) // 4),
-                             device=dy.device)
+            ws = L.scratch(L.lib().rs_act_bwd_colsum_workspace_size(B, fo), dy.device)
             L.call("rs_act_bwd_colsum", L.ptr(dy), L.ptr(y), B, fo, act, L.ptr(dz), L.ptr(db),
-                   L.ptr(ws), ws.numel() * 4, L.stream_ptr(dy.device))
+                   L.ptr(ws), ws.numel(), L.stream_ptr(dy.device))
         else:
             dz = dy
         dx = None
@@ -358,10 +357,9 @@ class _SharedInputDenseFn(torch.autograd.Function):
             g = torch.zeros(B, n, device=y.device) if g is None else g
             if g.stride(-1) != 1:
                 g = g.contiguous()
-            ws = torch.empty(max(1, L.lib().rs_act_bwd_colsum_workspace_size(B, n) // 4),
-                             device=y.device)
+            ws = L.scratch(L.lib().rs_act_bwd_colsum_workspace_size(B, n), y.device)
             L.call("rs_act_bwd_colsum_ld", L.ptr(g), g.stride(0), L.ptr(y[:, o:]), Nt, B, n,
-                   ctx.act, L.ptr(dz[:, o:]), Nt, L.ptr(db[o:]), L.ptr(ws), ws.numel() * 4,
+                   ctx.act, L.ptr(dz[:, o:]), Nt, L.ptr(db[o:]), L.ptr(ws), ws.numel(),
                    L.stream_ptr(y.device))
             o += n
         dx = None
@@ -447,10 +445,9 @@ def chain_reduce(x, dy, y, act, need_g=True):
     if x.stride(1) == 1 and (vec_ok or (nl > 1 and nl <= 256 and n0 <= 32)):
         out = torch.empty(n0 * nl + nl, device=dy.device, dtype=torch.float32)
         G = torch.empty_like(dy) if need_g else None
-        nb = L.lib().rs_chain_reduce_workspace_size(B, n0, nl)
-        ws = torch.empty(max(1, nb // 4), device=dy.device)
+        ws = L.scratch(L.lib().rs_chain_reduce_workspace_size(B, n0, nl), dy.device)
         L.call("rs_chain_reduce", L.ptr(x), x.stride(0), n0, L.ptr(dy), L.ptr(y), nl, act, B,
-               L.ptr(out), L.ptr(G), L.ptr(ws), ws.numel() * 4, L.stream_ptr(dy.device))
+               L.ptr(out), L.ptr(G), L.ptr(ws), ws.numel(), L.stream_ptr(dy.device))
         if G is None and act == 0 and need_g:
             G = dy
         return G, out[:n0 * nl].view(n0, nl), out[n0 * nl:]
@@ -459,9 +456,9 @@ def chain_reduce(x, dy, y, act, need_g=True):
     if act:
         G = torch.empty_like(dy)
         s = torch.empty(nl, device=dy.device, dtype=torch.float32)
-        ws = torch.empty(max(1, L.lib().rs_act_bwd_colsum_workspace_size(B, nl) // 4), device=dy.device)
+        ws = L.scratch(L.lib().rs_act_bwd_colsum_workspace_size(B, nl), dy.device)
         L.call("rs_act_bwd_colsum", L.ptr(dy), L.ptr(y), B, nl, act, L.ptr(G), L.ptr(s),
-               L.ptr(ws), ws.numel() * 4, L.stream_ptr(dy.device))
+               L.ptr(ws), ws.numel(), L.stream_ptr(dy.device))
     return G, wgrad(x, G), (s if s is not None else G.sum(0))
 
 

@@ -36,18 +36,8 @@ def keras_adam_coefficients(step: int, lr=1e-3, beta1=0.9, beta2=0.999, epsilon=
                         float(f(f(1) - f(beta2))), float(f(epsilon)))
 
 
-class _Workspace:
-    """Grow-only device scratch buffers keyed by name."""
-
-    def __init__(self):
-        self.bufs: dict[str, torch.Tensor] = {}
-
-    def get(self, name, nbytes, device):
-        b = self.bufs.get(name)
-        if b is None or b.numel() < nbytes or b.device != device:
-            b = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-            self.bufs[name] = b
-        return b
+# the class lives in _lib; this name stays importable for tests/test_embedding_gpu.py
+_Workspace = L.Workspace
 
 
 class SortedIds:
@@ -55,13 +45,13 @@ class SortedIds:
     (uint32 bits in int32), original positions, device count of distinct valid rows."""
 
     def __init__(self, ids: torch.Tensor, n_rows: int, slot_offsets: torch.Tensor | None = None,
-                 err_flag: torch.Tensor | None = None, ws: _Workspace | None = None,
+                 err_flag: torch.Tensor | None = None, ws: L.Workspace | None = None,
                  count_unique: bool = True, world: int = 1, valid: torch.Tensor | None = None,
                  max_slot_rows: int | None = None):
         """valid (uint8 [n], optional): positions with 0 are left out (sentinel key, no flag).
         max_slot_rows: the largest slot's row count (host-known; Embedding.max_slot_rows) — it
         lets a slab whose slots are all < 2^24 rows take the slot-segmented sort."""
-        ws = ws or _Workspace()
+        ws = ws or L.Workspace()
         ids = ids.contiguous()
         L.require_device(ids, "ids")
         n = ids.numel()
@@ -107,17 +97,17 @@ class SortedIds:
         return self
 
     @classmethod
-    def for_table(cls, table: Embedding, ids: torch.Tensor, ws: _Workspace | None = None,
+    def for_table(cls, table: Embedding, ids: torch.Tensor, ws: L.Workspace | None = None,
                   count_unique: bool = True, valid: torch.Tensor | None = None):
         return cls(ids, table.input_dim, table.slot_offsets, table.err_flag, ws, count_unique,
                    valid=valid, max_slot_rows=getattr(table, "max_slot_rows", None))
 
 
 def dedup_grad(table: Embedding, ids: torch.Tensor, grad_rows: torch.Tensor,
-               ws: _Workspace | None = None, sorted_ids: SortedIds | None = None):
+               ws: L.Workspace | None = None, sorted_ids: SortedIds | None = None):
     """(uniq_rows int64 [U], uniq_grad [U, dim]) — the deduplicated IndexedSlices gradient.
     Synchronises once to read U."""
-    ws = ws or _Workspace()
+    ws = ws or L.Workspace()
     dev = table.weight.device
     s = sorted_ids or SortedIds.for_table(table, ids, ws)
     n, dim = s.n, table.output_dim
@@ -153,7 +143,7 @@ class SparseOptimizer:
         self.tables = list(tables)
         self.lr = lr
         self.iterations = 0
-        self.ws = _Workspace()
+        self.ws = L.Workspace()
         self.fused = fused
         self.defer_join = bool(defer_join) and fused
         self.side = None
@@ -201,7 +191,7 @@ class SparseOptimizer:
         dev = ids.device
         if self.sort_stream is None:
             self.sort_stream = torch.cuda.Stream(device=dev)
-            self.sort_ws = _Workspace()
+            self.sort_ws = L.Workspace()
         ss = self.sort_stream
         L.stream_wait_stream(ss, torch.cuda.current_stream(dev), self._dev_event("sort_in"))
         with torch.cuda.stream(ss):
@@ -620,7 +610,7 @@ class FusedKerasAdam(GraphKerasAdam):
 
 
 def densify_grad(table: Embedding, ids: torch.Tensor, grad_rows: torch.Tensor,
-                 ws: _Workspace | None = None, valid: torch.Tensor | None = None,
+                 ws: L.Workspace | None = None, valid: torch.Tensor | None = None,
                  out: torch.Tensor | None = None) -> torch.Tensor:
     """The IndexedSlices gradient as a dense [input_dim, dim] tensor with no host sync. Small
     tables (input_dim·dim <= 16384): rs_embedding_grad_dense_small (one pass, fixed block /
@@ -631,7 +621,7 @@ def densify_grad(table: Embedding, ids: torch.Tensor, grad_rows: torch.Tensor,
     gradient is written there (every element) instead of into a new tensor. grad_rows may be a
     list of 1-4 [N_i, dim] row views (Embedding.take_grad(segments=True): one per lookup, row
     stride free, unit column stride), read in place as if concatenated."""
-    ws = ws or _Workspace()
+    ws = ws or L.Workspace()
     dev = table.weight.device
     dim, V = table.output_dim, table.input_dim
     if out is not None and (tuple(out.shape) != (V, dim) or out.dtype != torch.float32

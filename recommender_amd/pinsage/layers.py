@@ -159,7 +159,8 @@ class _MultiHotMeanFn(torch.autograd.Function):
         N, G = ctx.items.numel(), ctx.mh.shape[1]
         dev = g.device
         dtable = torch.empty(V, D, device=dev)
-        ws = _ws("multihot_bwd", L.lib().rs_multihot_mean_bwd_workspace_size(N, V, D), dev)
+        ws = L.workspace("pinsage.multihot_bwd",
+                         L.lib().rs_multihot_mean_bwd_workspace_size(N, V, D), dev)
         L.call("rs_multihot_mean_bwd", L.ptr(ctx.mh), G, ctx.mh.shape[0], L.ptr(ctx.items), N,
                L.ptr(g.contiguous()), V, D, L.ptr(dtable), L.ptr(tm.err_flag), L.ptr(ws),
                ws.numel(), L.stream_ptr(dev))
@@ -167,16 +168,7 @@ class _MultiHotMeanFn(torch.autograd.Function):
         return None, None, None, None
 
 
-_ws_bufs: dict = {}
 _aranges: dict = {}
-
-
-def _ws(name, nbytes, dev):
-    b = _ws_bufs.get((name, dev))
-    if b is None or b.numel() < nbytes:
-        b = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
-        _ws_bufs[(name, dev)] = b
-    return b
 
 
 def _arange_i32(n, dev):

@@ -34,17 +34,6 @@ def check_oob(dev) -> None:
                             "kernels read a zero row and dropped its gradient)")
 
 
-_ws_bufs: dict = {}
-
-
-def _ws(name, nbytes, dev):
-    b = _ws_bufs.get((name, dev))
-    if b is None or b.numel() < nbytes:
-        b = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
-        _ws_bufs[(name, dev)] = b
-    return b
-
-
 class _GatherRowsFn(torch.autograd.Function):
     """h.index_select(0, idx) whose backward is a fixed-order index_add (rs_index_add_rows:
     sort + tiled segmented sum) — run-to-run identical, where index_select's backward adds
@@ -63,7 +52,7 @@ class _GatherRowsFn(torch.autograd.Function):
         n, D = idx.numel(), g.shape[1]
         dev = g.device
         dh = torch.empty(ctx.n_rows, D, device=dev, dtype=g.dtype)
-        ws = _ws("index_add", L.lib().rs_index_add_rows_workspace_size(n, D), dev)
+        ws = L.workspace("pinsage.index_add", L.lib().rs_index_add_rows_workspace_size(n, D), dev)
         L.call("rs_index_add_rows", L.ptr(idx), L.id_dtype_code(idx), n, None, L.ptr(g), D,
                ctx.n_rows, L.ptr(dh), L.ptr(oob_flag(dev)), L.ptr(ws), ws.numel(),
                L.stream_ptr(dev))
@@ -111,7 +100,7 @@ class _PairMarginFn(torch.autograd.Function):
         pos = torch.empty(P, device=dev)
         neg = torch.empty(P, device=dev)
         loss = torch.empty((), device=dev)
-        ws = _ws("pair_fwd", L.lib().rs_pair_margin_workspace_size(P), dev)
+        ws = L.workspace("pinsage.pair_fwd", L.lib().rs_pair_margin_workspace_size(P), dev)
         # a bool mask's bytes are the 0 / 1 flags the kernel reads
         L.call("rs_pair_margin_fwd", L.ptr(h), D, D, h.shape[0], L.ptr(ps), L.ptr(pd), L.ptr(ns),
                L.ptr(nd), P, float(delta), L.ptr(valid), L.ptr(n_valid), L.ptr(pos), L.ptr(neg),
@@ -126,7 +115,7 @@ class _PairMarginFn(torch.autograd.Function):
         P, D = ps.numel(), h.shape[1]
         dev = h.device
         dh = torch.empty_like(h)
-        ws = _ws("pair_bwd", L.lib().rs_pair_margin_bwd_workspace_size(P, D), dev)
+        ws = L.workspace("pinsage.pair_bwd", L.lib().rs_pair_margin_bwd_workspace_size(P, D), dev)
         L.call("rs_pair_margin_bwd", L.ptr(h), D, D, h.shape[0], L.ptr(ps), L.ptr(pd), L.ptr(ns),
                L.ptr(nd), P, ctx.delta, L.ptr(valid), L.ptr(n_valid), L.ptr(pos), L.ptr(neg),
                L.ptr(g.reshape(1).contiguous()), L.ptr(dh), L.ptr(oob_flag(dev)), L.ptr(ws),

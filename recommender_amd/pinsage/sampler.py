@@ -23,25 +23,13 @@ from .. import _lib as L
 from .graph import Block, HeteroGraph, PairGraph
 
 
-class _Scratch:
-    def __init__(self):
-        self.bufs = {}
-
-    def get(self, name, nbytes, device):
-        b = self.bufs.get(name)
-        if b is None or b.numel() < nbytes:
-            b = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-            self.bufs[name] = b
-        return b
-
-
 def item_pairs(g: HeteroGraph, batch: int, seed: int, step: int, pair_base: int = 0,
-               scratch: _Scratch | None = None):
+               scratch: L.Workspace | None = None):
     dev = g.device
     heads, pos, neg = (torch.empty(batch, dtype=torch.int32, device=dev) for _ in range(3))
     n_valid = torch.zeros(1, dtype=torch.int32, device=dev)
-    scratch = scratch or _Scratch()
-    ws = scratch.get("pairs", L.lib().rs_item_pairs_workspace_size(batch), dev)
+    scratch = scratch or L.Workspace()
+    ws = scratch.get("pairs", L.lib().rs_item_pairs_workspace_size(batch), heads.device)
     L.call("rs_item_pairs", *(L.ptr(t) for t in g.csr_args()), g.n_items, pair_base, batch,
            seed, step & 0xFFFFFFFF, L.ptr(heads), L.ptr(pos), L.ptr(neg), L.ptr(n_valid),
            L.ptr(ws), ws.numel(), L.stream_ptr(dev))
@@ -54,7 +42,7 @@ def item2item_batch_sampler(g: HeteroGraph, utype: str, itype: str, batch_size: 
     """Yields (heads, pos_tails, neg_tails) int32 device tensors forever
     (pinsage/train/data_loader.py:6-18). With world > 1, rank r draws pairs
     [r*batch_size, (r+1)*batch_size) of the global batch of world*batch_size."""
-    scratch = _Scratch()
+    scratch = L.Workspace()
     step = 0
     while True:
         yield item_pairs(g, batch_size, seed, step, rank * batch_size, scratch)
@@ -86,7 +74,7 @@ class PinSageSampler:
         self.weight_column = weight_column
         self.seed = int(seed)
         self.step = 0
-        self.scratch = _Scratch()
+        self.scratch = L.Workspace()
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=g.device)
 
     # -- pieces ------------------------------------------------------------------------------
@@ -138,7 +126,8 @@ class PinSageSampler:
         n_edges = torch.zeros(1, dtype=torch.int32, device=dev)
         t_indptr = torch.empty(n_src + 1, dtype=torch.int32, device=dev)
         t_edge = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        ws = self.scratch.get("block", L.lib().rs_pinsage_block_workspace_size(n_dst, k), dev)
+        ws = self.scratch.get("block", L.lib().rs_pinsage_block_workspace_size(n_dst, k),
+                              nbr.device)
         L.call("rs_pinsage_block", L.ptr(nbr_local), L.ptr(cnt), n_dst, k, n_src, L.ptr(indptr),
                L.ptr(edge_src), L.ptr(edge_dst), L.ptr(edge_w), L.ptr(n_edges), L.ptr(t_indptr),
                L.ptr(t_edge), L.ptr(ws), ws.numel(), L.stream_ptr(dev))
@@ -209,7 +198,7 @@ class PinSageSampler:
         heads, pos, neg = (self._buf(n, (batch,), torch.int32) for n in ("heads", "pos", "neg"))
         n_valid = self._buf("n_valid", (1,), torch.int32)
         n_valid.zero_()
-        ws = self.scratch.get("pairs", L.lib().rs_item_pairs_workspace_size(batch), dev)
+        ws = self.scratch.get("pairs", L.lib().rs_item_pairs_workspace_size(batch), heads.device)
         if step_dev is None:
             L.call("rs_item_pairs", *(L.ptr(t) for t in self.g.csr_args()), self.g.n_items,
                    pair_base, batch, seed, step & 0xFFFFFFFF, L.ptr(heads), L.ptr(pos),
@@ -297,7 +286,7 @@ class PinSageSampler:
         t_indptr = self._buf(pre + "t_indptr", (cap_src + 1,), torch.int32)
         t_edge = self._buf(pre + "t_edge", (E,), torch.int32)
         ws = self.scratch.get("block." + pre, L.lib().rs_pinsage_block_workspace_size(cap_dst, k),
-                              dev)
+                              dst.device)
         L.call("rs_pinsage_block", L.ptr(nbr_local), L.ptr(cnt), cap_dst, k, cap_src,
                L.ptr(indptr), L.ptr(edge_src), L.ptr(edge_dst), L.ptr(edge_w), L.ptr(n_edges),
                L.ptr(t_indptr), L.ptr(t_edge), L.ptr(ws), ws.numel(), L.stream_ptr(dev))

@@ -21,7 +21,8 @@ import time
 import numpy as np
 import torch
 
-from ..optim import GraphKerasAdam, KerasAdam, SparseAdam, _Workspace, dedup_grad, densify_grad
+from .._lib import Workspace
+from ..optim import GraphKerasAdam, KerasAdam, SparseAdam, dedup_grad, densify_grad
 from ..synthetic import ML20M, movielens_graph
 from .evaluation import (build_val_test_matrix, get_item_reprs, hit_rate_eval, recommend,
                          train_test_split_by_time)
@@ -100,7 +101,7 @@ class PinSageStep:
         if getattr(self, "opt_graph", None) is None:
             self.opt_graph = GraphKerasAdam(self.dense + [t.weight for t in tables],
                                             lr=self.opt_dense.param_groups[0]["lr"])
-            self._ws = _Workspace()
+            self._ws = Workspace()
             self.opt_sparse.release_state()  # the graph path's Adam state is opt_graph's
         for p in self.dense:
             p.grad = None

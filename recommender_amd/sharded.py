@@ -39,7 +39,7 @@ from torch import nn
 
 from . import _lib as L
 from .embedding import Embedding
-from .optim import SortedIds, SparseOptimizer, _Workspace
+from .optim import SortedIds, SparseOptimizer
 
 
 class Comm:
@@ -137,7 +137,7 @@ class ShardedSlabEmbedding(nn.Module):
         self.register_buffer("err_flag", torch.zeros(1, dtype=torch.int32, device=device))
         self.grad_handle = nn.Parameter(torch.zeros(0, device=device), requires_grad=True)
         self.view = _UniqueRows(self)
-        self.ws = _Workspace()
+        self.ws = L.Workspace()
         self.side = torch.cuda.Stream(device=device) if device.type == "cuda" else None
         # exchange_begin's own stream: a later step's sort / unique / packing / row-id all-to-all
         # read no table state, so they run beside this step's exchange and apply instead of

@@ -12,7 +12,7 @@ from tests import adagrad_ref as R
 def test_constants_and_export(lib):
     assert L.RS_OPT_ADAGRAD == 3 and L.RS_OPT_ROWWISE_ADAGRAD == 4
     assert hasattr(lib, "rs_apply_adagrad")
-    assert "rs_apply_adagrad" in L.header_symbols() and "rs_apply_adagrad" in L._SIGS
+    assert "rs_apply_adagrad" in L.header_symbols() and "rs_apply_adagrad" in L.SIGNATURES
     text = L.HEADER.read_text()
     assert "#define RS_OPT_ADAGRAD 3" in text and "#define RS_OPT_ROWWISE_ADAGRAD 4" in text
 

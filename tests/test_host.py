@@ -17,7 +17,169 @@ def test_library_exports_header_symbols(lib):
 
 
 def test_every_header_symbol_has_a_python_signature():
-    assert set(L.header_symbols()) <= set(L._SIGS)
+    assert set(L.header_symbols()) <= set(L.SIGNATURES)
+
+
+_I32, _I64, _P, _SZ = C.c_int32, C.c_int64, C.c_void_p, C.c_size_t
+
+SYNTHETIC_HEADER = """
+/* a comment with a declaration in it: int32_t rs_fake(int x); */
+#ifndef SYNTHETIC_H
+#define SYNTHETIC_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define RS_THREE 3
+#define RS_MINUS_TWO (-2) /* parenthesised */
+#define RS_HEX 0x10       // sixteen; int32_t rs_fake(int x);
+#define RS_NOT_A_NUMBER "text"
+typedef struct rs_some_point {
+  float x, y, z; /* a run */
+  const int32_t* idx;
+  float* rows[3];
+  int64_t n;
+} rs_some_point;
+// int32_t rs_fake(int x);
+const char* rs_name(void);
+void* rs_make(void);
+size_t rs_size(int64_t n, int32_t d);
+int32_t rs_go(const float* a, float const* b, uint32_t k, uint64_t seed, float eps,
+              const rs_some_point* p, const float* const* many, void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif /* SYNTHETIC_H */
+"""
+
+
+def test_header_reader_on_a_synthetic_header():
+    from recommender_amd._header import read_header
+
+    consts, structs, funcs = read_header(SYNTHETIC_HEADER)
+    assert consts == {"RS_THREE": 3, "RS_MINUS_TWO": -2, "RS_HEX": 16}
+    assert list(structs) == ["rs_some_point"]
+    pt = structs["rs_some_point"]
+    assert pt.__name__ == "SomePoint" and issubclass(pt, C.Structure)
+    assert pt._fields_ == [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("idx", _P),
+                           ("rows", _P * 3), ("n", _I64)]
+    assert funcs == {
+        "rs_name": (C.c_char_p, []),
+        "rs_make": (_P, []),
+        "rs_size": (_SZ, [_I64, _I32]),
+        "rs_go": (_I32, [_P, _P, C.c_uint32, C.c_uint64, C.c_float, C.POINTER(pt), _P, _P]),
+    }
+    assert list(funcs) == ["rs_name", "rs_make", "rs_size", "rs_go"]
+
+
+@pytest.mark.parametrize("decl, named", [
+    ("int32_t rs_bad_param(const float* a, double x);", "rs_bad_param"),
+    ("void rs_bad_return(void);", "rs_bad_return"),
+    ("int32_t rs_by_value(rs_some_point p);", "rs_by_value"),
+    ("int32_t rs_unnamed(int32_t, float);", "rs_unnamed"),
+    ("typedef struct rs_bad_struct { double d; } rs_bad_struct;", "rs_bad_struct"),
+])
+def test_header_reader_refuses_what_it_cannot_type(decl, named):
+    from recommender_amd._header import read_header
+
+    text = SYNTHETIC_HEADER.replace("const char* rs_name(void);", decl)
+    with pytest.raises(ValueError, match=named):
+        read_header(text)
+
+
+def test_header_reader_on_the_real_header():
+    import re
+
+    F = C.c_float
+    assert len(L.SIGNATURES) >= 170
+    # the names, by the plain regex the binding used before it read whole declarations
+    text = L.HEADER.read_text()
+    names = set(re.findall(r"^\s*(?:const\s+)?[\w\s\*]+?\b(rs_\w+)\s*\(", text, re.M))
+    assert set(L.header_symbols()) == names == set(L.SIGNATURES)
+    assert L.header_symbols() == sorted(names)
+    assert L.SIGNATURES["rs_embedding_fwd"] == (
+        _I32, [_P, _I64, _I32, _P, _I32, _I64, _P, _I32, _P, _P, _P])
+    assert L.SIGNATURES["rs_bce_fwd"] == (_I32, [_P, _P, _I64, F, _I32, _P, _P, _SZ, _P])
+    assert L.SIGNATURES["rs_dlrm_dense_tail"] == (_I32, [C.POINTER(L.DlrmTailArgs), _P, _SZ, _P])
+    assert L.SIGNATURES["rs_last_error"] == (C.c_char_p, [])
+    assert L.SIGNATURES["rs_event_create"] == (_P, [])
+    assert L.SIGNATURES["rs_keras_adam_flat"][1][7] is C.POINTER(L.AdamParams)
+
+
+def test_load_sets_the_header_signatures(lib):
+    for name, (res, args) in L.SIGNATURES.items():
+        f = getattr(lib, name)
+        assert f.restype is res and list(f.argtypes) == args, name
+
+
+def test_struct_layout_matches_the_host_compiler(tmp_path):
+    """sizeof and every offsetof of the two argument structs, as g++ (the host compiler of
+    recommender_amd/build.py) lays them out from the header, against the generated ctypes."""
+    import subprocess
+
+    structs = {"rs_adam_params": L.AdamParams, "rs_dlrm_tail_args": L.DlrmTailArgs}
+    assert [f[0] for f in L.AdamParams._fields_] == ["lr", "beta1", "beta2", "one_minus_beta1",
+                                                     "one_minus_beta2", "epsilon"]
+    assert len(L.DlrmTailArgs._fields_) == 29 and L.DlrmTailArgs._fields_[-1] == ("lr", C.c_float)
+    lines = ["#include <cstddef>", "#include <cstdio>", '#include "recsys_hip.h"', "int main() {"]
+    for cname, cls in structs.items():
+        lines.append(f'  std::printf("{cname} sizeof %zu\\n", sizeof({cname}));')
+        lines += [f'  std::printf("{cname} {n} %zu\\n", offsetof({cname}, {n}));'
+                  for n, _ in cls._fields_]
+    src, exe = tmp_path / "layout.cpp", tmp_path / "layout"
+    src.write_text("\n".join(lines + ["  return 0;", "}"]) + "\n")
+    subprocess.run(["g++", "-std=c++17", f"-I{L.HEADER.parent}", str(src), "-o", str(exe)],
+                   check=True, capture_output=True, text=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    got = [tuple(line.split()) for line in out.splitlines()]
+    want = []
+    for cname, cls in structs.items():
+        want.append((cname, "sizeof", str(C.sizeof(cls))))
+        want += [(cname, n, str(getattr(cls, n).offset)) for n, _ in cls._fields_]
+    assert got == want
+    prm = L.AdamParams(1e-3, 0.9, 0.999, 0.1, 0.001, 1e-7)  # positional, as bench.py builds it
+    assert (prm.lr, prm.epsilon) == (C.c_float(1e-3).value, C.c_float(1e-7).value)
+
+
+def test_header_constants_are_module_attributes():
+    import re
+
+    defs = re.findall(r"^#define\s+(RS_\w+)\s+\(?(-?\d+)\)?", L.HEADER.read_text(), re.M)
+    assert len(defs) >= 18
+    for name, value in defs:
+        assert getattr(L, name) == int(value), name
+    assert (L.RS_ID_I32, L.RS_ID_I64, L.RS_DEDUP_TILE, L.RS_DIEN_SKIP_MASKED_ROWS) == (0, 1, 32, 1)
+    assert (L.RS_OPT_SGD, L.RS_OPT_LAZY_ADAM, L.RS_OPT_KERAS_ADAM) == (0, 1, 2)
+    assert (L.RS_ERRBIT_OOB, L.RS_ERRBIT_FORMAT, L.RS_ERRBIT_RANGE) == (1, 2, 4)
+    assert L.RS_E_INVALID == -1 and L.RS_E_UNSUPPORTED == -5
+
+
+def test_workspace_buffers_on_cpu_tensors():
+    import torch
+
+    cpu, meta = torch.device("cpu"), torch.device("meta")
+    ws = L.Workspace()
+    a = ws.get("a", 1000, cpu)
+    assert a.dtype == torch.uint8 and a.numel() == 1000 and a.device == cpu
+    assert ws.get("a", 10, cpu) is a and ws.get("a", 1000, cpu) is a  # smaller or equal: reused
+    big = ws.get("a", 1001, cpu)
+    assert big is not a and big.numel() == 1001 and ws.get("a", 1000, cpu) is big  # grow-only
+    assert ws.get("small", 1, cpu).numel() == 256  # the floor
+    b = ws.get("b", 1001, cpu)
+    assert b.data_ptr() != big.data_ptr() and ws.get("a", 1, cpu) is big  # names never alias
+    other = ws.get("a", 8, meta)
+    assert other.device == meta and other is not big  # another device: a new buffer
+    assert L.Workspace().get("a", 1001, cpu).data_ptr() != big.data_ptr()  # nor do two owners
+    # the process-wide buffers: one per (name, device)
+    s = L.workspace("test_host.x", 300, cpu)
+    assert L.workspace("test_host.x", 200, cpu) is s
+    assert L.workspace("test_host.y", 300, cpu).data_ptr() != s.data_ptr()
+    assert L.workspace("test_host.x", 300, meta).device == meta
+    assert L.workspace("test_host.x", 300, cpu) is s  # the other device did not displace it
+    # a fresh buffer of exactly the bytes asked for, at least one
+    f = L.scratch(10, cpu)
+    assert f.dtype == torch.uint8 and f.numel() == 10 and L.scratch(0, cpu).numel() == 1
+    assert L.scratch(10, cpu).data_ptr() != f.data_ptr()
 
 
 def test_build_id_matches_sources_and_stale_library_is_refused(lib):
