@@ -26,15 +26,17 @@ import torch
 
 from .. import _lib as L
 from ..functional import binary_crossentropy
-from ..nn import invalidate_compose_cache, overlapped_param_grads, overlapped_weight_grads
+from ..nn import overlapped_param_grads, overlapped_weight_grads
 from ..metrics import AUC
 from ..optim import DLRMScheduler, KerasAdam, SparseAdagrad, SparseAdam, SparseSGD
+from ..steps import StaticKerasAdam, allreduce_mean_, capture_graph, dense_parameters
 from ..synthetic import criteo_batch, criteo_cardinalities
 from .model import DLRM, DeepFM
 
 
 class TrainStep:
     """One optimizer step of a ctr model: forward, BCE, backward, dense + sparse apply."""
+    _static = None  # steps.StaticKerasAdam, built by the first static_step
 
     def __init__(self, model, optimizer="sgd", lr=None, loss_reduction="mean", sched=None,
                  fused=True, overlap_wgrad=False, comm=None, defer_sparse_join=False,
@@ -53,8 +55,7 @@ class TrainStep:
 
         self.model = model
         self.comm = comm
-        dense = [p for n, p in model.named_parameters() if not n.endswith("grad_handle")]
-        self.dense = dense
+        self.dense = dense = dense_parameters(model)
         emb = model.embedding_layer
         self.sharded = isinstance(emb, ShardedSlabEmbedding)
         tables = [emb.shard if self.sharded else emb]
@@ -103,44 +104,40 @@ class TrainStep:
         if self.sharded:
             emb.set_optimizer(self.opt_sparse)
 
-    def capture(self, batch, warmup: int = 3):
-        """Capture one whole step (forward, loss, backward, dense + sparse apply) on `batch`'s
-        tensors into a HIP graph; returns a replay callable. Scalars (learning rates) are
-        frozen into the graph, so capture only with constant-lr SGD."""
+    def _capture_sgd(self, defer_join, warm, body):
+        """capture / capture_sequence: run warm() on a side stream, then record body() into a HIP
+        graph with the sparse optimizer's defer_join set to `defer_join` for both."""
         if self._sched is not None or not isinstance(self.opt_sparse, SparseSGD):
             raise RuntimeError("graph capture needs constant-lr SGD (scalars are frozen)")
         if self.sharded:
             raise RuntimeError("a row-sharded slab's step reads its spill / late-round sizes on "
                                "the host each step and cannot be captured")
-        # the graph must join every stream it forks: the sparse update joins inside the step
-        # (a replay is ordered after the previous one as a whole)
         defer = self.opt_sparse.defer_join
-        self.opt_sparse.defer_join = False
+        self.opt_sparse.defer_join = defer_join
         torch.cuda.synchronize()
         for t in self.opt_sparse.tables:
             t._pending_update = None
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self(batch)
+            warm()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        invalidate_compose_cache()  # the graph must record the compositions it reads
-        with torch.cuda.graph(g):
-            loss = self(batch)
-        invalidate_compose_cache()
-        self._graph_loss = loss
+        replay = capture_graph(body)
         self.opt_sparse.defer_join = defer
-
-        def replay():
-            g.replay()
-            # the replay moved the parameters in place (no version bump): eager steps recompose
-            invalidate_compose_cache()
-            return loss
-
         return replay
+
+    def capture(self, batch, warmup: int = 3):
+        """Capture one whole step (forward, loss, backward, dense + sparse apply) on `batch`'s
+        tensors into a HIP graph; returns a replay callable. Scalars (learning rates) are
+        frozen into the graph, so capture only with constant-lr SGD."""
+        def warm():
+            for _ in range(warmup):
+                self(batch)
+
+        # the graph must join every stream it forks: the sparse update joins inside the step
+        # (a replay is ordered after the previous one as a whole)
+        return self._capture_sgd(False, warm, lambda: self(batch))
 
     def capture_sequence(self, batches, warmup: int = 2):
         """Capture len(batches) consecutive steps into ONE HIP graph (constant-lr SGD): no host
@@ -148,106 +145,43 @@ class TrainStep:
         overlaps the next step's bottom MLP exactly as the deferred join does eagerly; only the
         last step's update is joined at the end of the graph. Returns a replay callable that
         runs all the steps and returns the last loss."""
-        if self._sched is not None or not isinstance(self.opt_sparse, SparseSGD):
-            raise RuntimeError("graph capture needs constant-lr SGD (scalars are frozen)")
-        if self.sharded:
-            raise RuntimeError("a row-sharded slab's step reads its spill / late-round sizes on "
-                               "the host each step and cannot be captured")
-        defer = self.opt_sparse.defer_join
-        self.opt_sparse.defer_join = self.opt_sparse.fused
-        torch.cuda.synchronize()
-        for t in self.opt_sparse.tables:
-            t._pending_update = None
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
+        def steps(n):
+            loss = None
+            for _ in range(n):
                 for b in batches:
-                    self(b)
-            for t in self.opt_sparse.tables:
+                    loss = self(b)
+            for t in self.opt_sparse.tables:  # join the last update (inside the graph)
                 t.wait_update()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        invalidate_compose_cache()
-        with torch.cuda.graph(g):
-            for b in batches:
-                loss = self(b)
-            for t in self.opt_sparse.tables:  # join the last update inside the graph
-                t.wait_update()
-        invalidate_compose_cache()
-        self.opt_sparse.defer_join = defer
-
-        def replay():
-            g.replay()
-            invalidate_compose_cache()
             return loss
 
-        return replay
+        return self._capture_sgd(self.opt_sparse.fused, lambda: steps(warmup), lambda: steps(1))
 
     # -- graph-capturable Keras-Adam step (non-fused tables: DeepFM, cfg1) -------------------
     def static_step(self, batch):
-        """One Keras-Adam step with no host-side per-step scalars, so it can sit in a HIP graph
-        (as DIENStep.static_step): the table's IndexedSlices gradient densified (densify_grad:
-        the sort + tiled segmented sum of the sparse apply, no sync) into the flat gradient buffer
-        and Keras Adam over every variable with lr_t from device memory (GraphKerasAdam). Keras'
-        sparse Adam decays m / v and moves every row each step anyway, so this dense step is the
-        same update as __call__'s sparse apply + dense sweep (tests/test_deepfm_gpu.py: bit for
-        bit). Its Adam state is its own: do not interleave with __call__."""
-        from ..optim import GraphKerasAdam, densify_grad
-
+        """One Keras-Adam step that can sit in a HIP graph (steps.StaticKerasAdam): the same
+        update as __call__'s sparse apply + dense sweep (tests/test_deepfm_gpu.py: bit for bit).
+        Its Adam state is its own: do not interleave with __call__."""
         if (not isinstance(self.opt_sparse, SparseAdam) or self.opt_sparse.kind != L.RS_OPT_KERAS_ADAM
                 or self.opt_sparse.fused or self.sharded):
             raise RuntimeError("static_step: Keras Adam on non-fused, unsharded tables only")
-        tables = list(self.opt_sparse.tables)
-        if getattr(self, "opt_graph", None) is None:
-            tw = {id(t.weight) for t in tables}
-            self._gdense = [p for p in self.dense if id(p) not in tw and p.numel() > 0]
-            self.opt_graph = GraphKerasAdam(self._gdense + [t.weight for t in tables],
-                                            lr=self.opt_dense.param_groups[0]["lr"])
-            self._gws = L.Workspace()
-            self.opt_sparse.release_state()  # the graph path's Adam state is opt_graph's
-        for p in self._gdense:
-            p.grad = None
+        if self._static is None:
+            self._static = StaticKerasAdam(self.dense, self.opt_sparse.tables, self.opt_sparse,
+                                           self.opt_dense.param_groups[0]["lr"])
+            self.opt_graph = self._static.opt
+        self._static.zero_grad()
         cat, dense_x, label = batch
         pred = self.model({"cat_features": cat, "int_features": dense_x})
         self.last_pred = pred.detach()
         loss = binary_crossentropy(label, pred, reduction=self.loss_reduction)
         loss.backward()
-        grads = [p.grad for p in self._gdense]  # None: Keras skips the variable
-        nd = len(self._gdense)
-        for i, t in enumerate(tables):  # densified straight into the flat gradient buffer
-            got = t.take_grad(with_valid=True, segments=True)
-            grads.append(densify_grad(t, got[0], got[1], self._gws, valid=got[2],
-                                      out=self.opt_graph.grad_view(nd + i))
-                         if got is not None else None)
-        if not torch.cuda.is_current_stream_capturing():
-            self.opt_graph.prepare()
-            self.opt_graph.iterations += 1
-        self.opt_graph.apply(grads)
+        self._static.step()
         return loss.detach()
 
     def capture_static(self, batch):
         """Record one static_step on `batch` (static device tensors the caller refills before
         each replay) into a HIP graph; returns replay() -> loss. Run one eager static_step first
         (it builds the optimizer state the graph reads)."""
-        opt = self.opt_graph
-        opt.prepare()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        invalidate_compose_cache()  # the graph must record the compositions it reads
-        with torch.cuda.graph(g):
-            out = self.static_step(batch)
-        invalidate_compose_cache()
-        self._static_graph = g
-
-        def replay():
-            opt.prepare()
-            g.replay()
-            opt.iterations += 1
-            invalidate_compose_cache()  # the replay moved the parameters in place
-            return out
-        return replay
+        return self._static.capture(lambda: self.static_step(batch))
 
     def prefetch(self, batch):
         """Sort a LATER batch's ids now (Embedding.prefetch, fused sparse optimizer; on a
@@ -335,7 +269,8 @@ class TrainStep:
             else:
                 loss.backward()
         if self.comm is not None and self.comm.world > 1:
-            self._allreduce_dense()
+            # every dense gradient (≈3 MB for the DLRM MLPs) in one RCCL all-reduce
+            allreduce_mean_(self.comm, [p.grad for p in self.dense if p.grad is not None])
         self.opt_dense.step()
         if self.sharded:
             self.model.embedding_layer.join()
@@ -343,15 +278,6 @@ class TrainStep:
         else:
             self.opt_sparse.step()
         return loss
-
-    def _allreduce_dense(self):
-        """One bucketed RCCL all-reduce of every dense gradient (≈3 MB for the DLRM MLPs),
-        averaged over ranks — the MirroredStrategy dense-gradient sync."""
-        grads = [p.grad for p in self.dense if p.grad is not None]
-        flat = torch._utils._flatten_dense_tensors(grads)
-        self.comm.all_reduce_(flat)
-        flat.mul_(1.0 / self.comm.world)
-        torch._foreach_copy_(grads, list(torch._utils._unflatten_dense_tensors(flat, grads)))
 
 
 def build_model(model_type, embedding_size, vocab_size, num_cat_fea, num_int_fea, device,

@@ -12,10 +12,10 @@ import time
 import numpy as np
 import torch
 
-from .._lib import Workspace
 from ..functional import binary_crossentropy
 from ..metrics import AUC
-from ..optim import GraphKerasAdam, KerasAdam, SparseAdam, densify_grad
+from ..optim import KerasAdam, SparseAdam
+from ..steps import StaticKerasAdam, dense_parameters
 from . import DIEN, DIN, BaseModel
 
 
@@ -42,11 +42,13 @@ def synthetic_batch(rng, batch, hist_len, item_vocab, cat_vocab, negatives=True)
 
 
 class DIENStep:
+    _static = None  # steps.StaticKerasAdam, built by the first static_step
+
     def __init__(self, model, lr=1e-3):
         self.model = model
         tables = [model.item_embedding, model.cat_embedding]
-        dense = [p for n, p in model.named_parameters() if not n.endswith("grad_handle")]
-        self.opt_dense = KerasAdam(dense, lr=lr)
+        self.dense = dense_parameters(model)
+        self.opt_dense = KerasAdam(self.dense, lr=lr)
         self.opt_sparse = SparseAdam(tables, lr=lr, mode="keras")
         self.is_dien = isinstance(model, DIEN)
 
@@ -69,24 +71,14 @@ class DIENStep:
 
     # -- graph-capturable step --------------------------------------------------------------
     def static_step(self, feats, label):
-        """__call__ with no host-side per-step scalars, so it can sit in a HIP graph: the two
-        tables' IndexedSlices gradients densified (densify_grad: the same sort + tiled
-        segmented sum as the sparse apply, no sync) and Keras Adam over every variable with
-        lr_t from device memory (GraphKerasAdam, a variable without a gradient skipped as Keras
-        skips it). Keras' sparse Adam decays m / v and moves every row each step anyway, so the
-        dense step is the same update (tests/test_dien_step_gpu.py: equal to __call__ bit for
-        bit). Its Adam state is its own: do not interleave with __call__."""
-        tables = [self.model.item_embedding, self.model.cat_embedding]
-        if getattr(self, "opt_graph", None) is None:
-            tw = {id(t.weight) for t in tables}
-            self._gdense = [p for p in self.opt_dense.param_groups[0]["params"]
-                            if id(p) not in tw and p.numel() > 0]
-            self.opt_graph = GraphKerasAdam(self._gdense + [t.weight for t in tables],
-                                            lr=self.opt_dense.param_groups[0]["lr"])
-            self._ws = Workspace()
-            self.opt_sparse.release_state()  # the graph path's Adam state is opt_graph's
-        for p in self._gdense:
-            p.grad = None
+        """__call__ as a Keras-Adam step that can sit in a HIP graph (steps.StaticKerasAdam;
+        tests/test_dien_step_gpu.py: equal to __call__ bit for bit). Its Adam state is its own:
+        do not interleave with __call__."""
+        if self._static is None:
+            self._static = StaticKerasAdam(self.dense, self.opt_sparse.tables, self.opt_sparse,
+                                           self.opt_dense.param_groups[0]["lr"])
+            self.opt_graph = self._static.opt
+        self._static.zero_grad()
         if self.is_dien:
             pred, aux = self.model(feats, training=True)
             aux = aux.mean()
@@ -96,37 +88,14 @@ class DIENStep:
             total = aux = binary_crossentropy(label, pred, reduction="mean")
         self.last_pred = pred.detach()
         total.backward()
-        grads = [p.grad for p in self._gdense]  # None: Keras skips the variable
-        nd = len(self._gdense)
-        for i, t in enumerate(tables):  # densified straight into the flat gradient buffer
-            got = t.take_grad(with_valid=True, segments=True)
-            grads.append(densify_grad(t, got[0], got[1], self._ws, valid=got[2],
-                                      out=self.opt_graph.grad_view(nd + i))
-                         if got is not None else None)
-        if not torch.cuda.is_current_stream_capturing():
-            self.opt_graph.prepare()
-            self.opt_graph.iterations += 1
-        self.opt_graph.apply(grads)
+        self._static.step()
         return total.detach(), aux.detach()
 
     def capture(self, feats, label):
         """Record one static_step on (feats, label) — static device tensors the caller refills
         before each replay — into a HIP graph; returns replay() -> (total, aux). Run at least
         one eager static_step first (it builds the optimizer state the graph reads)."""
-        opt = self.opt_graph
-        opt.prepare()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            out = self.static_step(feats, label)
-        self._graph = g
-
-        def replay():
-            opt.prepare()
-            g.replay()
-            opt.iterations += 1
-            return out
-        return replay
+        return self._static.capture(lambda: self.static_step(feats, label))
 
 
 def main(argv=None):

@@ -15,8 +15,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .._lib import Workspace
-from ..optim import GraphKerasAdam, SparseAdam, densify_grad
+from ..optim import SparseAdam
+from ..steps import StaticKerasAdam
 from .model import EGES, GES, DeepWalk
 from .sampler import EGESPairSampler
 
@@ -58,6 +58,8 @@ def synthetic_batch(rng, batch, n_items, n_cat, n_brand, num_ns=5):
 
 
 class EGESStep:
+    _static = None  # steps.StaticKerasAdam, built by the first static_step
+
     def __init__(self, model, lr=1e-3):
         self.model = model
         self.opt = SparseAdam(model.tables(), lr=lr, mode="keras")
@@ -71,50 +73,23 @@ class EGESStep:
 
     # -- graph-capturable step --------------------------------------------------------------
     def static_step(self, inputs, labels):
-        """The same step with no host-side per-step scalars, so it can sit in a HIP graph:
-        every table's IndexedSlices gradient densified (densify_grad, no sync) and Keras Adam
-        over all of them with lr_t from device memory (GraphKerasAdam, one launch). Keras'
-        sparse Adam decays m / v and moves every row each step anyway (the dense sweep), so the
-        dense step is the same update. Its Adam state is its own: do not interleave with
-        __call__."""
-        tables = self.model.tables()
-        if getattr(self, "opt_graph", None) is None:
-            self.opt_graph = GraphKerasAdam([t.weight for t in tables], lr=self.opt.lr)
-            self._ws = Workspace()
-            self.opt.release_state()  # the graph path's Adam state is opt_graph's
+        """The same step as a Keras-Adam step that can sit in a HIP graph
+        (steps.StaticKerasAdam over the tables). Its Adam state is its own: do not interleave
+        with __call__."""
+        if self._static is None:
+            self._static = StaticKerasAdam([], self.opt.tables, self.opt, self.opt.lr)
+            self.opt_graph = self._static.opt
         logits = self.model(inputs)
         loss = F.binary_cross_entropy_with_logits(logits, labels)
         loss.backward()
-        grads = []
-        for i, t in enumerate(tables):  # densified straight into the flat gradient buffer
-            got = t.take_grad(segments=True)
-            grads.append(densify_grad(t, got[0], got[1], self._ws,
-                                      out=self.opt_graph.grad_view(i)) if got is not None
-                         else None)
-        if not torch.cuda.is_current_stream_capturing():
-            self.opt_graph.prepare()
-            self.opt_graph.iterations += 1
-        self.opt_graph.apply(grads)
+        self._static.step()
         return loss.detach()
 
     def capture(self, inputs, labels):
         """Record one static_step on (inputs, labels) — static device tensors the caller
         refills before each replay — into a HIP graph; returns replay() -> loss tensor. Run at
         least one eager static_step first."""
-        opt = self.opt_graph
-        opt.prepare()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            loss = self.static_step(inputs, labels)
-        self._graph = g
-
-        def replay():
-            opt.prepare()
-            g.replay()
-            opt.iterations += 1
-            return loss
-        return replay
+        return self._static.capture(lambda: self.static_step(inputs, labels))
 
 
 def build(model_type, n_items, n_cat, n_brand, embedding_size=160, device="cuda", generator=None):

@@ -17,6 +17,7 @@ import torch
 from ..functional import binary_crossentropy
 from ..metrics import AUC
 from ..optim import FusedKerasAdam, KerasAdam, SparseAdam, SparseSGD
+from ..steps import allreduce_mean_, dense_parameters
 from ..synthetic import aliccp_batch, scaled_vocab
 from . import ESMM, FEAT_VOCAB, MMOE, BaseModel
 
@@ -48,8 +49,7 @@ class MultiTaskStep:
         (touched rows only) or "sgd"."""
         self.model = model
         self.comm = comm
-        dense = [p for n, p in model.named_parameters() if not n.endswith("grad_handle")]
-        self.dense = dense
+        self.dense = dense = dense_parameters(model)
         slab = model.embedding_layer.slab
         table = getattr(slab, "shard", slab)
         if optimizer == "sgd":
@@ -84,7 +84,7 @@ class MultiTaskStep:
         loss = binary_crossentropy(label, y, reduction="mean")
         loss.backward()
         if self.comm is not None and self.comm.world > 1:
-            self._allreduce_dense()
+            allreduce_mean_(self.comm, [p.grad for p in self.dense if p.grad is not None])
         self.opt_dense.step()
         if self.sharded:
             self.model.embedding_layer.slab.join()
@@ -98,13 +98,6 @@ class MultiTaskStep:
         state, bit for bit); a no-op otherwise."""
         if hasattr(self.opt_sparse, "materialize"):
             self.opt_sparse.materialize()
-
-    def _allreduce_dense(self):
-        grads = [p.grad for p in self.dense if p.grad is not None]
-        flat = torch._utils._flatten_dense_tensors(grads)
-        self.comm.all_reduce_(flat)
-        flat.mul_(1.0 / self.comm.world)
-        torch._foreach_copy_(grads, list(torch._utils._unflatten_dense_tensors(flat, grads)))
 
 
 def train(argv=None):

@@ -21,8 +21,8 @@ import time
 import numpy as np
 import torch
 
-from .._lib import Workspace
-from ..optim import GraphKerasAdam, KerasAdam, SparseAdam, dedup_grad, densify_grad
+from ..optim import KerasAdam, SparseAdam, dedup_grad
+from ..steps import StaticKerasAdam
 from ..synthetic import ML20M, movielens_graph
 from .evaluation import (build_val_test_matrix, get_item_reprs, hit_rate_eval, recommend,
                          train_test_split_by_time)
@@ -55,6 +55,8 @@ def build_dataset(shape: dict, seed: int = 4, device="cuda"):
 
 
 class PinSageStep:
+    _static = None  # steps.StaticKerasAdam, built by the first static_step
+
     def __init__(self, model: PinSageModel, lr: float = 1e-3, comm=None):
         self.model = model
         self.dense = model.dense_parameters()
@@ -79,54 +81,28 @@ class PinSageStep:
     # -- sync-free step on capacity-shaped batches (PinSageSampler.sample_static) ------------
     def static_step(self, pos_graph, neg_graph, blocks):
         """One training step with no host sync, so it can be captured into a HIP graph: masked
-        margin loss over the live pairs, and Keras Adam (GraphKerasAdam: lr_t from device
-        memory) on the dense parameters and on the three tables' densified IndexedSlices
-        gradients — Keras' sparse Adam decays m / v and moves every row anyway
-        (_resource_apply_sparse [3p TF 2.2]), so the dense form is the same update. Equal to
-        __call__ on the unpadded batch up to fp32 rounding order (tests/test_pinsage_gpu.py).
-        Its Adam state (GraphKerasAdam) is its own: do not interleave with __call__.
+        margin loss over the live pairs, and the shared graph-capturable Keras Adam
+        (steps.StaticKerasAdam) on the dense parameters and the three tables. Equal to __call__
+        on the unpadded batch up to fp32 rounding order (tests/test_pinsage_gpu.py). Its Adam
+        state is its own: do not interleave with __call__.
 
         world > 1 (pairs sharded over the ranks, graph and tables replicated):
-        every gradient lands in GraphKerasAdam's one flat gradient buffer, which is all-reduced
-        (one collective: RCCL under nccl, so the sharded step captures into a HIP graph too) and
-        scaled 1/W before the Adam launch — MirroredStrategy's mean of the replicas' gradients
-        (pinsage/train/train.py:40-48), as __call__ does eagerly. The layout is fixed, so every
-        parameter must have a gradient on every rank (capacity-shaped batches look up every
-        table)."""
+        the flat gradient buffer is all-reduced and scaled 1/W before the Adam launch —
+        MirroredStrategy's mean of the replicas' gradients (pinsage/train/train.py:40-48), as
+        __call__ does eagerly. Every parameter must have a gradient on every rank
+        (capacity-shaped batches look up every table)."""
         if (self.world > 1 and getattr(self.comm, "staged", False)
                 and torch.cuda.is_current_stream_capturing()):
             raise ValueError("a gloo-staged all-reduce cannot be captured: capture the sharded "
                              "step under RCCL (nccl)")
-        tables = self.model.tables()
-        if getattr(self, "opt_graph", None) is None:
-            self.opt_graph = GraphKerasAdam(self.dense + [t.weight for t in tables],
-                                            lr=self.opt_dense.param_groups[0]["lr"])
-            self._ws = Workspace()
-            self.opt_sparse.release_state()  # the graph path's Adam state is opt_graph's
-        for p in self.dense:
-            p.grad = None
+        if self._static is None:
+            self._static = StaticKerasAdam(self.dense, self.opt_sparse.tables, self.opt_sparse,
+                                           self.opt_dense.param_groups[0]["lr"], comm=self.comm)
+            self.opt_graph = self._static.opt
+        self._static.zero_grad()
         loss = self.model.margin_loss(pos_graph, neg_graph, blocks, 1.0)
         loss.backward()
-        grads = [p.grad for p in self.dense]  # None: Keras skips the variable
-        nd = len(self.dense)
-        for i, t in enumerate(tables):  # densified straight into the flat gradient buffer
-            got = t.take_grad(segments=True)
-            grads.append(densify_grad(t, got[0], got[1], self._ws,
-                                      out=self.opt_graph.grad_view(nd + i)) if got is not None
-                         else None)
-        if self.comm is not None and self.comm.collective:
-            if any(g is None for g in grads):
-                raise ValueError("sharded static_step: a parameter has no gradient on this rank; "
-                                 "the all-reduce needs the same flat layout on every rank")
-            opt = self.opt_graph
-            opt.collect(grads)
-            self.comm.all_reduce_(opt.grad_flat)
-            opt.grad_flat.mul_(1.0 / self.world)
-            grads = [opt.grad_view(i) for i in range(len(grads))]
-        if not torch.cuda.is_current_stream_capturing():
-            self.opt_graph.prepare()
-            self.opt_graph.iterations += 1  # a capture records the step; replay() counts it
-        self.opt_graph.apply(grads)
+        self._static.step()
         return loss.detach()
 
     def capture(self, batch):
@@ -134,20 +110,7 @@ class PinSageStep:
         sampler's persistent buffers) into a HIP graph. Returns replay(): one training step on
         whatever the sampler last wrote into those buffers, and the step's loss tensor. Run at
         least one eager static_step first (library handles, workspaces)."""
-        opt = self.opt_graph
-        opt.prepare()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            loss = self.static_step(*batch)
-        self._graph = g
-
-        def replay():
-            opt.prepare()
-            g.replay()
-            opt.iterations += 1
-            return loss
-        return replay
+        return self._static.capture(lambda: self.static_step(*batch))
 
     def capture_with_sampling(self, sampler, batch_size: int, seed: int, step: int,
                               pair_base: int = 0):
@@ -159,27 +122,22 @@ class PinSageStep:
         dev = sampler.g.device
         pair_step = torch.tensor([step], dtype=torch.int32, device=dev)
         walk_step = torch.tensor([sampler.step], dtype=torch.int32, device=dev)
-        opt = self.opt_graph
-        opt.prepare()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
         host_step = sampler.step
-        with torch.cuda.graph(g):
+
+        def body():
             batch = sampler.sample_static(
                 *sampler.sample_pairs_static(batch_size, seed, 0, pair_base, step_dev=pair_step),
                 step_dev=walk_step)
             loss = self.static_step(*batch)
             pair_step.add_(1)
             walk_step.add_(1)
-        sampler.step = host_step  # the capture ran no step
-        self._graph = g
-
-        def replay():
-            opt.prepare()
-            g.replay()
-            opt.iterations += 1
-            sampler.step += 1
             return loss
+
+        def count():
+            sampler.step += 1
+
+        replay = self._static.capture(body, after_replay=count)
+        sampler.step = host_step  # the capture ran no step
         return replay
 
     def _allreduce_and_apply_tables(self):

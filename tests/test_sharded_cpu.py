@@ -1,5 +1,5 @@
 """CPU tests of the multi-rank path: the Comm transport and the dense-gradient all-reduce of
-TrainStep over a world-size-2 gloo group, and the sharded-step oracle against the unsharded one."""
+the trainers over a world-size-2 gloo group, and the sharded-step oracle against the unsharded one."""
 import os
 
 import numpy as np
@@ -32,20 +32,14 @@ def _worker(rank, world, port, q):
         t = torch.full((5,), float(rank + 1))
         c.all_reduce_(t)
         assert torch.equal(t, torch.full((5,), float(sum(range(1, world + 1)))))
-        # TrainStep's bucketed dense all-reduce (average over ranks)
-        from recommender_amd.ctr.train import TrainStep
+        # the trainers' bucketed dense all-reduce (average over ranks)
+        from recommender_amd.steps import allreduce_mean_
 
-        class Fake:
-            pass
-
-        ts = TrainStep.__new__(TrainStep)
-        ts.comm = c
         p1 = torch.nn.Parameter(torch.zeros(3, 2))
         p2 = torch.nn.Parameter(torch.zeros(4))
         p1.grad = torch.full((3, 2), float(rank))
         p2.grad = torch.full((4,), float(2 * rank))
-        ts.dense = [p1, p2]
-        ts._allreduce_dense()
+        allreduce_mean_(c, [p1.grad, p2.grad])
         m = (world - 1) / 2
         assert torch.allclose(p1.grad, torch.full((3, 2), m)) and torch.allclose(p2.grad, torch.full((4,), 2 * m))
         q.put((rank, "ok"))
