@@ -5,8 +5,10 @@
               with the oracle's NumPy step timed on the host beside it (cpu_baseline)
   cfg2 dlrm_cfg2: DLRM, 26 per-slot tables x 10M rows x D 64 in one 66.6 GB slab, B 8192,
               bottom [512, 256, 64], top [512, 256, 1], Zipf(1.05) ids, --optimizer sgd|lazy_adam|keras_adam
+  pinsage_infer: whole-catalogue PinSage inference at the ML-20M shape (get_item_reprs(32) against
+              the layer-wise chain, unfused and fused) and the convolve alone on a 4M-item table
 Prints one JSON line per run with examples/sec and per-kernel HIP-event times.
-Usage: python benchmarks/bench_models.py --model dien|mmoe|esmm|deepfm|dlrm_cfg2 [--steps K --warmup W]"""
+Usage: python benchmarks/bench_models.py --model dien|mmoe|esmm|deepfm|dlrm_cfg2|pinsage_infer [--steps K --warmup W]"""
 from __future__ import annotations
 
 import argparse
@@ -45,7 +47,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="dien",
                     choices=["dien", "mmoe", "esmm", "deepfm", "deepfm_file", "pinsage", "eges",
-                             "dlrm_cfg2"])
+                             "dlrm_cfg2", "pinsage_infer"])
+    ap.add_argument("--infer-items", type=int, default=4_000_000,
+                    help="pinsage_infer: items of the synthetic table the convolve alone is timed on")
     ap.add_argument("--file-rows", type=int, default=1_000_000,
                     help="deepfm_file: rows of the Criteo-shaped TFRecord file written and trained on")
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "lazy_adam", "keras_adam"],
@@ -92,6 +96,8 @@ def main():
     L.load()
     if args.model == "deepfm_file":
         return deepfm_from_file(args)
+    if args.model == "pinsage_infer":
+        return pinsage_infer_bench(args)
     if args.tuned_gemms == 1 or (args.tuned_gemms < 0 and args.model in ("dien", "esmm", "mmoe")):
         from recommender_amd.gemm_tuning import use_tuned_gemms
 
@@ -390,6 +396,130 @@ def main():
                            "floor_ms_at_peak": round(floor_ms, 3),
                            "note": "the whole step's time over its dense GEMM FLOPs (embedding, "
                                    "apply and elementwise work included in the time)"}
+    print(json.dumps(out))
+
+
+def _interleaved_ms(fns: dict, warmup: int, reps: int):
+    """{name: [ms per call]} for callables timed with device events, one call of each per round
+    (A B A B ...), so drift of the shared machine lands on every variant alike."""
+    for _ in range(warmup):
+        for f in fns.values():
+            f()
+    torch.cuda.synchronize()
+    ms = {n: [] for n in fns}
+    for _ in range(reps):
+        for n, f in fns.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            f()
+            e.record()
+            e.synchronize()
+            ms[n].append(s.elapsed_time(e))
+    return ms
+
+
+def _spread(v):
+    v = sorted(v)
+    return {"median_ms": round(v[len(v) // 2], 4), "min_ms": round(v[0], 4),
+            "max_ms": round(v[-1], 4), "calls": len(v)}
+
+
+def pinsage_infer_bench(args):
+    """Whole-catalogue PinSage inference (recommender_amd/pinsage/inference.py).
+    (a) The ML-20M-shaped graph of pinsage/train.py, every item's representation three ways:
+        evaluation.get_item_reprs in batches of 32 (sampler + model per batch), the layer-wise
+        chain on the existing kernels (fused=False) and on rs_pinsage_infer_layer (fused).
+        Host clock around whole calls ending in a synchronise; the neighbour table and the
+        features are part of both layer-wise figures.
+    (b) The convolve alone on a synthetic --infer-items table (d_in 24, hidden 32, d_out 16,
+        k 3, uniform random neighbours), fused against unfused, interleaved in one process,
+        device events per call. The unfused path is handed its CSR prebuilt (not timed). Bytes
+        per item: the fused layer 4·d_in + 8k + 4k·hidden + 4·d_out plus fc_1's 4·d_in +
+        4·hidden; the fraction of the 8 TB/s HBM peak is those bytes over the median time.
+        layer_fused_near_neighbors is the fused layer on a table whose neighbours sit within 64
+        rows of their item (the same algorithmic bytes, the gathered lines served by the caches)."""
+    from recommender_amd.pinsage import PinSageModel, PinSageSampler
+    from recommender_amd.pinsage import inference as I
+    from recommender_amd.pinsage.evaluation import get_item_reprs
+    from recommender_amd.pinsage.train import ML20M, build_graph
+
+    dev = "cuda"
+    reps = max(args.steps, 3)
+    out = {"workload": "pinsage_infer", "steps": reps, "warmup": args.warmup}
+    # ---- (a) ML-20M shape ------------------------------------------------------------------
+    g = build_graph(ML20M, 4)
+    m = PinSageModel(g, g.itype, 2, 8, 32, 16)
+    smp = PinSageSampler(g, g.itype, g.utype, 2, 2, 4, 0.0, 3, seed=4)
+
+    def host_ms(fn, warm, n):
+        for _ in range(warm):
+            fn()
+        v = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            v.append((time.perf_counter() - t0) * 1e3)
+        return v
+
+    ways = {"get_item_reprs_b32": (lambda: get_item_reprs(m, smp, g, g.itype, 32), 1, 3),
+            "layerwise_unfused": (lambda: I.infer_item_reprs(m, smp, fused=False), args.warmup, reps),
+            "layerwise_fused": (lambda: I.infer_item_reprs(m, smp), args.warmup, reps)}
+    ml = {n: _spread(host_ms(f, w, r)) for n, (f, w, r) in ways.items()}
+    out["ml20m"] = {"n_items": g.n_items, "graph_edges": g.n_edges, **ml,
+                    "sampled_over_fused": round(ml["get_item_reprs_b32"]["median_ms"]
+                                                / ml["layerwise_fused"]["median_ms"], 1),
+                    "unfused_over_fused": round(ml["layerwise_unfused"]["median_ms"]
+                                                / ml["layerwise_fused"]["median_ms"], 3)}
+    del g, m, smp
+    # ---- (b) the convolve alone ----------------------------------------------------------------
+    n, d_in, hidden, d_out, k = args.infer_items, 24, 32, 16, 3
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(4)
+    h = torch.rand(n, d_in, device=dev, generator=gen) * 2 - 1
+    nbr = torch.randint(0, n, (n, k), device=dev, generator=gen, dtype=torch.int32)
+    cnt = torch.randint(1, 9, (n, k), device=dev, generator=gen, dtype=torch.int32)
+    nbr[::17, 2] = -1   # a share of empty slots, as dead ends leave
+    cnt[::17, 2] = 0
+    fc1 = (torch.rand(d_in, hidden, device=dev, generator=gen) - 0.5,
+           torch.rand(hidden, device=dev, generator=gen) * 0.1)
+    fc2 = (torch.rand(hidden + d_in, d_out, device=dev, generator=gen) - 0.5,
+           torch.rand(d_out, device=dev, generator=gen) * 0.1)
+    csr = I.neighbor_csr(nbr, cnt)
+    u = I._affine(h, fc1[0], fc1[1], 1)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    fns = {"convolve_fused": lambda: I.convolve(h, nbr, cnt, fc1, fc2, "relu", "row", True),
+           "convolve_unfused": lambda: I.convolve(h, nbr, cnt, fc1, fc2, "relu", "row", False, csr),
+           "layer_fused": lambda: I.layer_from_u(h, u, nbr, cnt, fc2[0], fc2[1], 1, "row", True, flag),
+           "layer_unfused": lambda: I.layer_from_u(h, u, nbr, cnt, fc2[0], fc2[1], 1, "row", False,
+                                                   flag, csr)}
+    # the same layer with every neighbour within 64 rows of its item: the gathered lines are
+    # the ones the neighbouring tiles read anyway, which separates the kernel's streaming rate
+    # from what the random 128-byte gathers cost
+    near = (torch.arange(n, device=dev).unsqueeze(1)
+            + torch.randint(-64, 65, (n, k), device=dev, generator=gen)).clamp_(0, n - 1).to(torch.int32)
+    fns["layer_fused_near_neighbors"] = lambda: I.layer_from_u(h, u, near, cnt, fc2[0], fc2[1], 1,
+                                                               "row", True, flag)
+    with torch.no_grad():
+        a = fns["convolve_fused"]()
+        b = fns["convolve_unfused"]()
+        diff = float((a - b).abs().max())
+        ms = {nm: _spread(v) for nm, v in _interleaved_ms(fns, args.warmup, reps).items()}
+    layer_b = 4 * d_in + 8 * k + 4 * k * hidden + 4 * d_out
+    conv_b = layer_b + 4 * d_in + 4 * hidden
+    conv = {"n_items": n, "sizes": [d_in, hidden, d_out, k], **ms,
+            "bytes_per_item": {"fused_layer": layer_b, "convolve_with_fc1": conv_b},
+            "max_abs_diff_fused_vs_unfused": diff}
+    for nm, by in (("convolve_fused", conv_b), ("layer_fused", layer_b),
+                   ("layer_fused_near_neighbors", layer_b)):
+        gbs = n * by / (ms[nm]["median_ms"] * 1e-3) / 1e9
+        conv[nm]["achieved_GBs"] = round(gbs, 1)
+        conv[nm]["frac_of_8TBs"] = round(gbs / 8000.0, 4)
+    conv["unfused_over_fused"] = {
+        "convolve": round(ms["convolve_unfused"]["median_ms"] / ms["convolve_fused"]["median_ms"], 3),
+        "layer": round(ms["layer_unfused"]["median_ms"] / ms["layer_fused"]["median_ms"], 3)}
+    out["convolve_alone"] = conv
     print(json.dumps(out))
 
 

@@ -822,6 +822,32 @@ int32_t rs_frobenius_normalize_rows_bwd(const float* dy, const float* y, const f
                                         const int32_t* n_rows, float* dx, void* workspace,
                                         size_t ws_bytes, void* stream);
 
+/* Layer-wise inference (pinsage/inference/inference.py:8-41, spark_function.py:29-34): one
+ * Convolve layer over every item, fused. The dst nodes are items 0..n_items-1 in order, the src
+ * nodes the same items, the block the neighbour table nbr / cnt [n_items, k] of
+ * rs_pinsage_neighbors (-1 / 0 = empty slot). Per item i, with no intermediate in HBM:
+ *   nv  = Σ_j (float)cnt[i,j] · u[nbr[i,j]] / max(Σ_j cnt[i,j], 1), slots in order (the
+ *         rs_weighted_mean_agg_fwd arithmetic); u = fc_1(h) [n_items, hidden]
+ *   z   = [nv ; h[i]] · w2 + b2 (w2 [(hidden + d_in), d_out], rows [nv ; h] as nn.Dense stores
+ *         fc_2's kernel), then relu when relu != 0
+ *   out[i] = z (norm 0) or z / ||z||_2 (norm 1).
+ * Deviation from the Spark UDF: a row whose norm is exactly 0 comes out as zeros, where
+ * l2norm's 0 / 0 gives NaN. A slot id other than -1 outside [0, n_items) is skipped and sets
+ * RS_ERRBIT_OOB in err_flag (may be NULL); a zero count on a valid id contributes nothing.
+ * A row depends on its own inputs only (no atomics, no cross-row reduction): the result is
+ * run-to-run identical and independent of n_items and of the tiling. A block owns tiles of
+ * RS_PINSAGE_INFER_TILE consecutive items. Shapes past RS_PINSAGE_INFER_MAX_* return
+ * RS_E_UNSUPPORTED (callers compose rs_weighted_mean_agg_fwd and the Dense layers instead). */
+#define RS_PINSAGE_INFER_TILE 64
+#define RS_PINSAGE_INFER_MAX_DIN 192
+#define RS_PINSAGE_INFER_MAX_HIDDEN 64
+#define RS_PINSAGE_INFER_MAX_DOUT 64
+#define RS_PINSAGE_INFER_MAX_K 32
+int32_t rs_pinsage_infer_layer(const float* h, int64_t n_items, int32_t d_in, const float* u,
+                               int32_t hidden, const int32_t* nbr, const int32_t* cnt, int32_t k,
+                               const float* w2, const float* b2, int32_t d_out, int32_t relu,
+                               int32_t norm, float* out, int32_t* err_flag, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * EGES / GES / DeepWalk (eges/model.py).
  * Skip-gram logits, fused gather + dot (DeepWalk.call :26-36, GES.call :58-64):

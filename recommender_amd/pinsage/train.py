@@ -11,7 +11,9 @@ all-reduce averages the dense grads together with the densified table grads. Gra
 synthetic: MovieLens-shaped (recommender_amd.synthetic.movielens_graph) with synthetic rating
 times; no dataset is reachable offline. Every `--eval_every` steps (test_steps = 1000,
 train.py:69,84-88) the device evaluation of pinsage/evaluation.py runs: item reprs →
-recommend(top_k 10) → hit-rate against the time-split validation matrix.
+recommend(top_k 10) → hit-rate against the time-split validation matrix. `--eval-reprs
+layerwise` takes the item reprs from pinsage/inference.py (every layer once over all items, the
+per-row norm of the reference's inference) instead of get_item_reprs' sampled batches of 32.
 """
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ from ..synthetic import ML20M, movielens_graph
 from .evaluation import (build_val_test_matrix, get_item_reprs, hit_rate_eval, recommend,
                          train_test_split_by_time)
 from .graph import HeteroGraph
+from .inference import infer_item_reprs
 from .model import PinSageModel, check_oob
 from .sampler import PinSageSampler, item_pairs
 
@@ -185,6 +188,10 @@ def main(argv=None):
     ap.add_argument("--hip_graph", type=int, default=1,
                     help="1: sync-free capacity-shaped batches, sampling + step replayed as one "
                          "HIP graph (PinSageStep.capture_with_sampling); 0: the DGL-shaped step")
+    ap.add_argument("--eval-reprs", choices=["sampled", "layerwise"], default="sampled",
+                    help="the evaluation's item representations: sampled = get_item_reprs "
+                         "(sampler + model, 32 seeds at a time); layerwise = "
+                         "inference.infer_item_reprs (each layer once over the whole catalogue)")
     args = ap.parse_args(argv)
     num_layers = 2
     embedding_size = 8
@@ -216,7 +223,10 @@ def main(argv=None):
             print(f"step {step} step_loss {float(loss):.4f}")
             check_oob(loss.device)  # the graph steps' out-of-range node ids, checked here
         if args.eval_every and step % args.eval_every == 0:
-            reprs = get_item_reprs(model, sampler, g, g.itype, 32)
+            if args.eval_reprs == "layerwise":
+                reprs = infer_item_reprs(model, sampler)
+            else:
+                reprs = get_item_reprs(model, sampler, g, g.itype, 32)
             recs = recommend(g, args.top_k, reprs, None, g.utype, "timestamp", 32)
             print(f"step {step} hit_rate {hit_rate_eval(recs, val_matrix.tocsr()):.4f}")
     torch.cuda.synchronize()
