@@ -169,7 +169,8 @@ int32_t rs_sort_ids_sharded(const void* ids, int32_t id_dtype, int64_t n_ids,
                             int32_t* n_unique, int32_t* err_flag, void* workspace, size_t ws_bytes,
                             void* stream);
 /* From sorted keys: uniq_keys[u] (ascending), inverse[p] = u of position p (-1 for an OOB id),
- * n_unique[1], and owner_counts[world] (unique keys per owner rank; may be NULL).
+ * n_unique[1], and owner_counts[world] (unique keys per owner rank; may be NULL). world <= 1024,
+ * as rs_sort_ids_sharded.
  * Workspace: rs_unique_inverse_workspace_size(n_ids) bytes; it begins with int32 [n_ids], the
  * exclusive scan of the head flags — each sorted key's segment (unique) index — which
  * rs_embedding_dedup_grad_mapped_range takes as seg_excl for the same sorted keys. */
@@ -262,8 +263,12 @@ int32_t rs_embedding_dedup_grad_mapped(const uint32_t* sorted_rows, const int32_
  * the whole key space n_rows, so two calls over adjoining ranges emit exactly the segments one
  * call does, with the same sums); seg_ready 1: the workspace already holds the segment ids of a
  * previous call on the same sorted keys; seg_excl (may be NULL): those segment ids given (the
- * head of rs_unique_inverse's workspace over the same keys), seg_ready then ignored. D = 128
- * with 16-byte aligned rows (the group walk).
+ * head of rs_unique_inverse's workspace over the same keys), seg_ready then ignored.
+ * Ranges by width: D = 128 with 16-byte aligned rows (the group walk) takes any
+ * 0 <= key_lo < key_hi <= n_rows; every other width or alignment takes the ranges that begin at
+ * key_lo = 0 only (the generic walk with key_hi as its row count: the keys from key_hi on are
+ * dropped like the OOB sentinel) and refuses key_lo != 0 with RS_E_UNSUPPORTED. A range that
+ * holds no key writes nothing.
  * The row-sharded step deduplicates its two owner halves apart, so the first half's gradient
  * all-to-all runs while the second half is summed. */
 int32_t rs_embedding_dedup_grad_mapped_range(const uint32_t* sorted_rows, const int32_t* sorted_pos,

@@ -1651,8 +1651,9 @@ extern "C" int32_t rs_unique_inverse(const uint32_t* sorted_keys, const int32_t*
                                      uint32_t* uniq_keys, int32_t* inverse, int32_t* n_unique,
                                      int32_t* owner_counts, void* workspace, size_t ws_bytes,
                                      void* stream) {
-  RS_CHECK_ARG(world >= 1 && n_rows > 0 && n_ids >= 0, "bad sizes");
-  RS_CHECK_ARG(n_ids == 0 || (sorted_keys && sorted_pos && uniq_keys && inverse && n_unique),
+  // world <= 1024 as rs_sort_ids_sharded: owner_counts_kernel is one block of a thread per owner
+  RS_CHECK_ARG(world >= 1 && world <= 1024 && n_rows > 0 && n_ids >= 0, "bad sizes");
+  RS_CHECK_ARG(n_unique && (n_ids == 0 || (sorted_keys && sorted_pos && uniq_keys && inverse)),
                "null pointer");
   hipStream_t st = as_stream(stream);
   const int64_t stride = ceil_div(n_rows, world);
