@@ -263,6 +263,130 @@ def embedding(iters, out):
     report("rs_embedding_fwd", cfg, us, ids.numel() * (4 + 2 * 4 * D), out)
 
 
+def embedding_bag(iters, out, rounds=5):
+    """EmbeddingBag against what it replaces, interleaved in one process (`rounds` rounds of every
+    variant, each timed over `iters` launches; medians reported, every round's time next to them).
+
+    (a) DIEN BASE history mean: B 4096, L 100, D 18, lengths U[1, 100], 63 001 items, [B, L] ids
+        with a valid mask. (b) multi-hot DLRM: 26 slots x B 8192 CSR bags, D 64, lengths
+        Geometric(1/8) capped at 64, over the cfg2 slab (26 x 10M rows).
+    Forward: rs_embedding_bag_fwd against rs_embedding_fwd + torch's masked pooling. Backward
+    (sort + apply, SGD and row-wise Adagrad, lr 0 so the table stays put): the sort remapped to
+    bags reading dout [n_bags, D], against torch expanding dout to [n_ids, D] rows for the
+    ordinary apply. Bytes, forward: live ids x (4 D + id bytes) + n_bags x 4 D. Backward: dout
+    once, 8 bytes of sorted key + position per id, each touched row read and written."""
+    rng = np.random.default_rng(4)
+    st = L.stream_ptr(torch.device(DEV))
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    shapes = []
+    # (a)
+    B, Lh, D, V = 4096, 100, 18, 63001
+    lens = rng.integers(1, Lh + 1, B)
+    valid = np.arange(Lh)[None, :] < lens[:, None]
+    ids = np.where(valid, rng.integers(1, V, (B, Lh)), 0).astype(np.int32)
+    shapes.append(dict(name="dien_base", V=V, D=D, n_bags=B, bag_len=Lh, ids=ids.reshape(-1),
+                       offsets=None, valid=valid.reshape(-1).astype(np.uint8), so=None,
+                       bag_of_pos=np.repeat(np.arange(B), Lh), lens=lens))
+    # (b)
+    S, B2, D2, per = 26, 8192, 64, 10_000_000
+    nb = S * B2
+    lens = np.minimum(rng.geometric(1 / 8, nb), 64)
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    ids = rng.integers(0, per, offs[-1]).astype(np.int32)
+    shapes.append(dict(name="multihot_cfg2", V=S * per, D=D2, n_bags=nb, bag_len=0, ids=ids,
+                       offsets=offs, valid=None, so=np.arange(S + 1, dtype=np.int64) * per,
+                       bag_of_pos=np.repeat(np.arange(nb), lens), lens=lens))
+    for sh in shapes:
+        V, D, nb, bl = sh["V"], sh["D"], sh["n_bags"], sh["bag_len"]
+        n = sh["ids"].size
+        table = torch.empty(V, D, device=DEV).uniform_(-0.05, 0.05)
+        ids = torch.from_numpy(sh["ids"]).to(DEV)
+        offs = None if sh["offsets"] is None else torch.from_numpy(sh["offsets"]).to(DEV)
+        valid = None if sh["valid"] is None else torch.from_numpy(sh["valid"]).to(DEV)
+        so = None if sh["so"] is None else torch.from_numpy(sh["so"]).to(DEV)
+        n_slots = 1 if so is None else so.numel() - 1
+        bag_of_pos = torch.from_numpy(sh["bag_of_pos"]).to(DEV)
+        # the baseline and both sorts take global rows (a slab bag's slot is bag % n_slots)
+        slot_lo = 0 if so is None else so[bag_of_pos % n_slots]
+        rows64 = (ids.long() + slot_lo).contiguous()
+        live = n if valid is None else int(valid.sum())
+        cfg = {"shape": sh["name"], "rows": V, "D": D, "n_bags": nb, "n_ids": n, "live_ids": live}
+        pooled = torch.empty(nb, D, device=DEV)
+        scale = torch.empty(nb, device=DEV)
+        gathered = torch.empty(n, D, device=DEV)
+        m = None if valid is None else valid.view(nb, bl, 1).float()
+
+        def bag_fwd():
+            L.call("rs_embedding_bag_fwd", L.ptr(table), V, D, L.ptr(ids), 0, n, L.ptr(offs), nb,
+                   bl, L.ptr(valid), None, L.RS_BAG_MEAN, L.ptr(so), n_slots, L.ptr(pooled), D,
+                   L.ptr(scale), L.ptr(err), st)
+
+        def base_fwd():
+            L.call("rs_embedding_fwd", L.ptr(table), V, D, L.ptr(rows64), 1, n, None, 1,
+                   L.ptr(gathered), L.ptr(err), st)
+            if m is not None:  # dien/layers.py compute_his_average
+                return (gathered.view(nb, bl, D) * m).sum(1) / m.sum(1)
+            return torch.zeros(nb, D, device=DEV).index_add_(0, bag_of_pos, gathered) * scale[:, None]
+
+        bag_fwd()
+        # backward
+        dout = torch.randn(nb, D, device=DEV)
+        s_rows = torch.empty(n, dtype=torch.int32, device=DEV)
+        s_pos = torch.empty(n, dtype=torch.int32, device=DEV)
+        bag_pos = torch.empty(n, dtype=torch.int32, device=DEV)
+        sws = torch.empty(L.lib().rs_sort_ids_workspace_size(n), dtype=torch.uint8, device=DEV)
+        aws = torch.empty(L.lib().rs_apply_workspace_size(n, D), dtype=torch.uint8, device=DEV)
+        acc_row = torch.full((V,), 0.1, device=DEV)
+        prm = L.AdamParams(0.0, 0.0, 0.0, 0.0, 0.0, 1e-7)
+
+        def sort():
+            L.call("rs_sort_ids_slots", L.ptr(rows64), 1, n, L.ptr(valid), None, 1, V, V,
+                   L.ptr(s_rows), L.ptr(s_pos), None, L.ptr(err), L.ptr(sws), sws.numel(), st)
+
+        def bag_bwd(opt, acc):
+            sort()
+            L.call("rs_embedding_bag_remap_pos", L.ptr(s_pos), n, L.ptr(offs), nb, bl,
+                   L.ptr(bag_pos), st)
+            L.call("rs_embedding_apply_scaled", opt, L.ptr(table), L.ptr(acc), None, V, D,
+                   L.ptr(s_rows), L.ptr(bag_pos), n, L.ptr(dout), L.ptr(scale), 1, prm, None,
+                   L.ptr(aws), aws.numel(), st)
+
+        def base_bwd(opt, acc):
+            g = (dout * scale[:, None])
+            if m is not None:   # the masked mean's backward: [B, L, D] rows, zero where masked
+                rows = (g.unsqueeze(1) * m).reshape(n, D)
+            else:               # index_add_'s backward: a gather of the pooled gradient
+                rows = g[bag_of_pos]
+            sort()
+            L.call("rs_embedding_apply", opt, L.ptr(table), L.ptr(acc), None, V, D, L.ptr(s_rows),
+                   L.ptr(s_pos), n, L.ptr(rows), prm, None, L.ptr(aws), aws.numel(), st)
+
+        variants = [("fwd", "bag", bag_fwd), ("fwd", "lookup+torch pool", base_fwd)]
+        for oname, opt, acc in (("sgd", L.RS_OPT_SGD, None),
+                                ("rowwise_adagrad", L.RS_OPT_ROWWISE_ADAGRAD, acc_row)):
+            variants.append((f"bwd[{oname}]", "bag", lambda o=opt, a=acc: bag_bwd(o, a)))
+            variants.append((f"bwd[{oname}]", "expanded", lambda o=opt, a=acc: base_bwd(o, a)))
+        variants.append(("sort", "shared by both backward paths", sort))
+        times = {v[:2]: [] for v in variants}
+        for _ in range(rounds):
+            for what, side, fn in variants:
+                times[(what, side)].append(timed(fn, iters))
+        uniq = int(torch.unique(rows64 if valid is None else rows64[valid != 0]).numel())
+        fwd_bytes = live * (4 * D + 4) + nb * 4 * D
+        bwd_bytes = nb * 4 * D + n * 8 + uniq * 8 * D
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        for what, side, _ in variants:
+            us = med[(what, side)]
+            extra = {"rounds_us": [round(t, 1) for t in times[(what, side)]]}
+            if side != "bag" and (what, "bag") in med:
+                extra["bag_over_this"] = round(med[(what, "bag")] / us, 3)
+            nbytes = fwd_bytes if what == "fwd" else (n * 16 if what == "sort" else bwd_bytes)
+            report(f"embedding_bag {what}: {side} (interleaved, median of {rounds})",
+                   dict(cfg, **extra), us, nbytes, out)
+        del table, gathered, acc_row
+        torch.cuda.empty_cache()
+
+
 def criteo(iters, out):
     """Criteo TSV ingestion: line index + parse + vocab lookup over a ~45 MB synthetic text
     (algorithmic bytes: text read once, outputs written once)."""

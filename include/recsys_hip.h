@@ -114,6 +114,65 @@ int32_t rs_embedding_fwd_strided(const float* table, int64_t n_rows, int32_t dim
                                  void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * a-1b  EmbeddingBag: jagged sum / mean lookup (torch.nn.EmbeddingBag's surface; the masked
+ * history mean of dien/layers.py:5-17 and the side-information mean of eges/model.py:74-80 are
+ * instances) and the two helpers of its backward.
+ *
+ * Bag layout. Bag b holds positions [offsets[b], offsets[b+1]) of ids; offsets is a device
+ *   int64 [n_bags+1]. offsets == NULL: every bag is bag_len consecutive positions, and
+ *   n_ids == n_bags * bag_len is checked on the host (padded [B, L] histories, fixed multi-hot);
+ *   no offsets array is read. A bag whose range is reversed or leaves [0, n_ids] is treated as
+ *   empty and sets RS_ERRBIT_OOB. Bags must not overlap.
+ * valid: uint8 [n_ids] or NULL; positions with 0 are skipped and do not count (the sorts' own
+ *   valid argument: one mask drives both directions).
+ * Slots: with slot_offsets ([n_slots+1]), bag b reads slot b % n_slots; the global row follows
+ *   rs_embedding_fwd's rule (row = slot_offsets[s] + id while id < that slot's row count).
+ *   An out-of-range id, negatives included, contributes a zero row, still counts, and sets
+ *   RS_ERRBIT_OOB.
+ * Arithmetic (fixed: results are bit-reproducible). Per column acc = +0.f; each live position,
+ *   in ascending position order, does acc = __fadd_rn(acc, t) with t the table element or, with
+ *   per_sample_weights (float [n_ids]), __fmul_rn(w[p], element) — never an fma. RS_BAG_SUM
+ *   writes acc, RS_BAG_MEAN writes acc / (float)count (IEEE division), count = the bag's live
+ *   positions. A bag with count == 0 writes +0.f: torch's convention (the reference's masked
+ *   mean divides by zero there and gives NaN). per_sample_weights with RS_BAG_MEAN is refused.
+ * out: row b at out + b * out_ld (floats), out_ld >= dim; only the dim columns are written.
+ * bag_scale [n_bags] (may be NULL when the caller has no use for it, e.g. RS_BAG_SUM): the
+ *   forward writes 1.0f / (float)count, 0 for an empty bag. It is the backward's row_scale.
+ * One lane group walks a bag from its first position to its last, so a bag of more than a few
+ *   hundred ids runs on that group alone; long bags are not split, because the fixed order of
+ *   the additions is part of this contract.
+ * Errors: RS_E_INVALID for null pointers, dim <= 0, a mode other than 0 / 1, out_ld < dim,
+ *   weights with RS_BAG_MEAN, n_ids != n_bags * bag_len without offsets.
+ *
+ * rs_embedding_bag_remap_pos: bag_pos[i] = the bag holding position sorted_pos[i] (pos / bag_len
+ *   without offsets, else a binary search over offsets); 0 where the position lies in no bag —
+ *   the sort must have dropped those positions (valid, or the sentinel key), so they are never
+ *   read. With bag_pos in place of sorted_pos, the pooled upstream gradient dout [n_bags, dim] as
+ *   grad_out and, for the mean, bag_scale as row_scale with scale_group = 1,
+ *   rs_embedding_apply_scaled performs the bag's backward: the [n_ids, dim] gradient never exists,
+ *   and the result equals, bit for bit, rs_embedding_apply on the expansion below.
+ * rs_embedding_bag_expand_grad: grad_rows[p] (contiguous [n_ids, dim]) = __fmul_rn(bag_scale[b],
+ *   dout[b]) for the bag b holding p (bag_scale NULL: dout[b] itself), then __fmul_rn(w[p], .)
+ *   with per_sample_weights; rows of positions outside every bag are zero. dout row b at
+ *   dout + b * dout_ld. Neither helper reads ids: no out-of-range flag, no err_flag. */
+#define RS_BAG_SUM 0
+#define RS_BAG_MEAN 1
+int32_t rs_embedding_bag_fwd(const float* table, int64_t n_rows, int32_t dim, const void* ids,
+                             int32_t id_dtype, int64_t n_ids, const int64_t* offsets,
+                             int64_t n_bags, int32_t bag_len, const uint8_t* valid,
+                             const float* per_sample_weights, int32_t mode,
+                             const int64_t* slot_offsets, int32_t n_slots, float* out,
+                             int64_t out_ld, float* bag_scale, int32_t* err_flag, void* stream);
+int32_t rs_embedding_bag_remap_pos(const int32_t* sorted_pos, int64_t n_ids,
+                                   const int64_t* offsets, int64_t n_bags, int32_t bag_len,
+                                   int32_t* bag_pos, void* stream);
+int32_t rs_embedding_bag_expand_grad(const float* dout, int64_t dout_ld, int32_t dim,
+                                     int64_t n_ids, const int64_t* offsets, int64_t n_bags,
+                                     int32_t bag_len, const float* bag_scale,
+                                     const float* per_sample_weights, float* grad_rows,
+                                     void* stream);
+
+/* ------------------------------------------------------------------------------------
  * a-2 (part 1) Duplicate-index coalescing: the IndexedSlices gradient's `unique` +
  * `unsorted_segment_sum` (Keras OptimizerV2 _deduplicate_indexed_slices, reached from
  * apply_gradients at ctr/train.py:97, dien/train.py:22, esmm/train.py:104).

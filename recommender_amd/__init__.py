@@ -6,3 +6,13 @@ host side mirrors the reference's Keras layer/model call surfaces (neoyinyao/Rec
 from . import _lib  # noqa: F401
 
 __version__ = "0.1.0"
+
+_TABLES = ("Embedding", "EmbeddingBag", "SlabEmbedding")
+
+
+def __getattr__(name):
+    # the table classes, importable from the package (resolved on first use)
+    if name in _TABLES:
+        from . import embedding
+        return getattr(embedding, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -16,15 +16,24 @@ import torch
 from torch import nn
 
 from ..embedding import Embedding
-from ..functional import embedding_lookup_concat
+from ..functional import embedding_bag, embedding_lookup_concat
 from .layers import (MLP, DIENAttention, InterestEvolve, InterestExtract, LocalActivationUnit,
                      attention_evolve, compute_his_average)
 
 
 class BaseModel(nn.Module):
     def __init__(self, item_vocab_size, item_embedding_size, cat_vocab_size, cat_embedding_size,
-                 mlp_units, device=None, generator=None):
+                 mlp_units, device=None, generator=None, pooled_history=False):
+        """pooled_history (BASE only): the history mean as two pooled lookups
+        (functional.embedding_bag, mode="mean", valid = the history mask) straight into one
+        [B, D] tensor; the [B, L, D] history rows and, in the backward, their [B·L, D] gradient are
+        never formed. Same sum in the same order as compute_his_average, divided once instead of
+        multiplied by a mask and divided, so equal up to rounding — except that an all-padding
+        history gives 0 where the default path gives NaN (0 / 0)."""
         super().__init__()
+        if pooled_history and type(self) is not BaseModel:
+            raise ValueError("pooled_history: BASE only (DIN and DIEN read the history rows)")
+        self.pooled_history = bool(pooled_history)
         D = item_embedding_size + cat_embedding_size
         self.embedding_dim = D
         self.mlp = MLP(mlp_units, "sigmoid", 2 * D, device, generator)
@@ -43,9 +52,23 @@ class BaseModel(nn.Module):
     def compute_prob(self, inputs):
         return self.forward(inputs)
 
+    def pooled_his_average(self, item, cat, mask):
+        """[mean of the item rows ‖ mean of the category rows] over each history's unmasked
+        steps, each pooled into its column block of one [B, D] tensor."""
+        di = self.item_embedding.output_dim
+        rep = torch.empty(item.shape[0], self.embedding_dim, device=self.item_embedding.weight.device,
+                          dtype=torch.float32)
+        valid = mask.to(torch.uint8)
+        embedding_bag(self.item_embedding, item, mode="mean", valid=valid, out=rep[:, :di])
+        embedding_bag(self.cat_embedding, cat, mode="mean", valid=valid, out=rep[:, di:])
+        return rep
+
     def forward(self, inputs, training=False, mask=None):
         mask = self.item_embedding.compute_mask(inputs["pos_his_item"])
         target = self.compute_flat_embedding((inputs["target_item"], inputs["target_cat"])).squeeze(1)
+        if self.pooled_history:
+            rep = self.pooled_his_average(inputs["pos_his_item"], inputs["pos_his_cat"], mask)
+            return self.mlp(torch.cat([target, rep], -1), training=training)
         his = self.compute_flat_embedding((inputs["pos_his_item"], inputs["pos_his_cat"]))
         rep = compute_his_average(his, mask)
         return self.mlp(torch.cat([target, rep], -1), training=training)

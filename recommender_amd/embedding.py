@@ -16,7 +16,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .functional import embedding_lookup
+from .functional import BagGrad, embedding_bag, embedding_lookup
 
 
 def check_err_flag(err_flag: torch.Tensor) -> int:
@@ -181,16 +181,40 @@ class Embedding(nn.Module):
         v = None if valid is None else valid.reshape(-1).to(torch.uint8)
         self._pending.append((ids.reshape(-1), grad_rows.reshape(-1, self.output_dim), v))
 
+    def accumulate_bag_grad(self, bag: BagGrad):
+        """A bag lookup's gradient, kept unexpanded (functional.BagGrad) in call order with the
+        other lookups'. take_bag_grad hands it to a sparse optimizer as it is; take_grad expands
+        it into an ordinary (ids, rows, valid) entry."""
+        self._pending.append(bag)
+
     def has_grad(self) -> bool:
         return bool(self._pending)
+
+    def take_bag_grad(self):
+        """The step's bag gradient when it is the table's sole contribution since the last take
+        and can go through the remapped apply (no per-sample weights); clears the pending list.
+        None otherwise, with the list untouched: take_grad then serves the step — lookups of one
+        step are concatenated and deduplicated once, never applied one after the other."""
+        p = self._pending
+        if len(p) == 1 and isinstance(p[0], BagGrad) and p[0].remappable:
+            self._pending = []
+            return p[0]
+        return None
 
     def take_grad(self, with_valid: bool = False, segments: bool = False):
         """(ids [N] flattened in position order, grad rows [N, dim]) of every lookup since the
         last call, concatenated in call order; clears the pending list. with_valid: a third
         entry, the uint8 [N] flags of positions that carry gradient (None when every lookup
         registered all its positions). segments: the grad rows of 2-4 lookups stay a list of the
-        lookups' own [N_i, dim] row views (densify_grad reads them in place, no concatenation)."""
+        lookups' own [N_i, dim] row views (densify_grad reads them in place, no concatenation).
+        A bag lookup's gradient arrives expanded (rs_embedding_bag_expand_grad)."""
         p, self._pending = self._pending, []
+        if any(isinstance(e, BagGrad) for e in p):
+            if self.slot_offsets is not None:
+                # an expanded entry's slot would be position % n_slots; a bag's is bag % n_slots
+                raise NotImplementedError("a slab table's bag gradient has no (ids, rows) form: "
+                                          "apply it with a sparse optimizer, one lookup per step")
+            p = [e.expand() if isinstance(e, BagGrad) else e for e in p]
         if not p:
             return None
         if len(p) == 1:
@@ -241,6 +265,26 @@ class Embedding(nn.Module):
 
     def extra_repr(self):
         return f"{self.input_dim}, {self.output_dim}, mask_zero={self.mask_zero}, slots={self.n_slots}"
+
+
+class EmbeddingBag(Embedding):
+    """torch.nn.EmbeddingBag's surface over an Embedding table: forward pools each bag's rows
+    into one (functional.embedding_bag; mode 'sum' or 'mean'). Takes every Embedding argument;
+    with slot_offsets the table is a slab of per-slot tables and bag b reads slot b % n_slots,
+    so a [B, n_slots] grid of multi-hot bags is one call."""
+
+    def __init__(self, input_dim: int, output_dim: int, mode: str = "mean", **kw):
+        super().__init__(input_dim, output_dim, **kw)
+        if mode not in ("sum", "mean"):
+            raise ValueError("mode must be 'sum' or 'mean'")
+        self.mode = mode
+
+    def forward(self, ids: torch.Tensor, offsets=None, valid=None, per_sample_weights=None):
+        return embedding_bag(self, ids, offsets, mode=self.mode, valid=valid,
+                             per_sample_weights=per_sample_weights)
+
+    def extra_repr(self):
+        return f"{super().extra_repr()}, mode={self.mode}"
 
 
 class SlabEmbedding(Embedding):

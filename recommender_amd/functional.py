@@ -124,6 +124,149 @@ def embedding_lookup(table_module, ids: torch.Tensor, grad_mask=None) -> torch.T
     return _EmbeddingLookup.apply(table_module.grad_handle, table_module, ids, grad_mask)
 
 
+BAG_MODES = {"sum": L.RS_BAG_SUM, "mean": L.RS_BAG_MEAN}
+
+
+class BagGrad:
+    """One bag lookup's gradient, unexpanded: the pooled upstream rows dout [n_bags, dim] with the
+    layout that says which positions of `ids` each bag holds. scale is the forward's bag_scale
+    (1 / count per bag) for the mean, None for the sum. A sparse optimizer applies it through the
+    remapped sort (SparseOptimizer.apply_bag); every other consumer gets expand()."""
+
+    def __init__(self, ids, offsets, n_bags, bag_len, valid, weights, scale, dout):
+        self.ids, self.offsets, self.n_bags, self.bag_len = ids, offsets, n_bags, bag_len
+        self.valid, self.weights, self.scale, self.dout = valid, weights, scale, dout
+
+    @property
+    def remappable(self) -> bool:
+        """The remapped apply multiplies by one scale per bag: the weighted sum always expands."""
+        return self.weights is None
+
+    def remap(self, sorted_pos: torch.Tensor) -> torch.Tensor:
+        """The bag of every sorted position (rs_embedding_bag_remap_pos)."""
+        bag_pos = torch.empty_like(sorted_pos)
+        L.call("rs_embedding_bag_remap_pos", L.ptr(sorted_pos), sorted_pos.numel(),
+               L.ptr(self.offsets), self.n_bags, self.bag_len, L.ptr(bag_pos),
+               L.stream_ptr(sorted_pos.device))
+        return bag_pos
+
+    def expand(self):
+        """(ids [n_ids], grad rows [n_ids, dim], valid) — the ordinary form of this gradient
+        (rs_embedding_bag_expand_grad)."""
+        d = self.dout
+        n = self.ids.numel()
+        rows = torch.empty(n, d.shape[1], device=d.device, dtype=torch.float32)
+        L.call("rs_embedding_bag_expand_grad", L.ptr(d), d.shape[1], d.shape[1], n,
+               L.ptr(self.offsets), self.n_bags, self.bag_len, L.ptr(self.scale),
+               L.ptr(self.weights), L.ptr(rows), L.stream_ptr(d.device))
+        return self.ids, rows, self.valid
+
+
+class _EmbeddingBag(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out, handle, table_module, ids, offsets, mode, valid, weights):
+        # `out` comes first: autograd rebases the history of a view modified in place on the
+        # function's first input
+        _wait_update(table_module)
+        w = table_module.weight
+        L.require_device(w, "embedding table")
+        ids = _ids_flat(ids)
+        dim = w.shape[1]
+        n = ids.numel()
+        if offsets is None:
+            if ids.dim() < 2:
+                raise ValueError("embedding_bag: ids [n_bags, L] when no offsets are given")
+            bag_len = ids.shape[-1]
+            n_bags = torch.Size(ids.shape[:-1]).numel()
+        else:
+            L.require_device(offsets, "offsets")
+            if ids.dim() != 1 or offsets.dim() != 1 or offsets.dtype != torch.int64 \
+                    or offsets.numel() < 1:
+                raise ValueError("embedding_bag: ids [n_ids] with offsets int64 [n_bags + 1]")
+            offsets = offsets.contiguous()
+            bag_len, n_bags = 0, offsets.numel() - 1
+        if valid is not None:
+            L.require_device(valid, "valid")
+            if valid.numel() != n:
+                raise ValueError("embedding_bag: valid holds one flag per id")
+            valid = valid.reshape(-1).to(torch.uint8).contiguous()
+        if weights is not None:
+            L.require_device(weights, "per_sample_weights")
+            if weights.numel() != n:
+                raise ValueError("embedding_bag: per_sample_weights holds one weight per id")
+            weights = weights.detach().reshape(-1).float().contiguous()
+        ctx.inplace = out is not None
+        if out is None:
+            out = torch.empty(n_bags, dim, device=w.device, dtype=torch.float32)
+        else:
+            L.require_device(out, "out")
+            if (tuple(out.shape) != (n_bags, dim) or out.dtype != torch.float32
+                    or (n_bags > 0 and out.stride(1) != 1)
+                    or (n_bags > 1 and out.stride(0) < dim)):
+                raise ValueError(f"embedding_bag: out must be float32 [{n_bags}, {dim}] rows")
+            ctx.mark_dirty(out)
+        scale = (torch.empty(n_bags, device=w.device, dtype=torch.float32)
+                 if mode == L.RS_BAG_MEAN else None)
+        so = table_module.slot_offsets
+        n_slots = 1 if so is None else so.numel() - 1
+        L.call("rs_embedding_bag_fwd", L.ptr(w), w.shape[0], dim, L.ptr(ids), L.id_dtype_code(ids),
+               n, L.ptr(offsets), n_bags, bag_len, L.ptr(valid), L.ptr(weights), mode, L.ptr(so),
+               n_slots, L.ptr(out), out.stride(0) if n_bags > 1 else dim, L.ptr(scale),
+               L.ptr(table_module.err_flag), L.stream_ptr(w.device))
+        ctx.table_module = table_module
+        ctx.bag = (ids.reshape(-1), offsets, n_bags, bag_len, valid, weights, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        tm = ctx.table_module
+        bag = BagGrad(*ctx.bag, grad_out.reshape(-1, grad_out.shape[-1]).contiguous())
+        opt = tm.fused_optimizer
+        if opt is not None:
+            opt.apply_bag_async(tm, bag)
+        else:
+            tm.accumulate_bag_grad(bag)
+        # the rows pooled over: their earlier contents have gradient zero (a defined one, or
+        # autograd would drop the gradient of the rest of the tensor `out` is a view of)
+        d_out = torch.zeros_like(grad_out) if ctx.inplace else None
+        return d_out, None, None, None, None, None, None, None
+
+
+def embedding_bag(table_module, ids: torch.Tensor, offsets: torch.Tensor | None = None, *,
+                  mode: str = "mean", valid: torch.Tensor | None = None,
+                  per_sample_weights: torch.Tensor | None = None,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """Pooled lookup (rs_embedding_bag_fwd): row b of the result is the sum or mean of the table
+    rows of bag b's ids, added in position order (bit-reproducible; include/recsys_hip.h).
+
+    ids [n_ids] with offsets (int64 [n_bags + 1] on the device; bag b = positions offsets[b] ..
+    offsets[b+1], the bags covering every position), or ids [n_bags, L] without: one bag per row.
+    valid (ids' shape): positions with 0 are skipped and do not count — a padded history's mask.
+    per_sample_weights (ids' shape, mode="sum" only, no gradient): each row scaled before it is
+    added. out: a float32 [n_bags, dim] row view (unit column stride) to pool into, e.g. a column
+    block of a wider tensor (item ‖ category without a concat); it is returned.
+    An empty bag gives a zero row (mean included: torch's convention, not the masked mean's NaN).
+    With a slab table, bag b reads slot b % n_slots.
+
+    Backward: the table's optimizer applies dout [n_bags, dim] through the sort's positions
+    remapped to bags (no [n_ids, dim] gradient), with a fused optimizer right away, otherwise in
+    step() when the bag is the table's only lookup of the step; other consumers get it expanded."""
+    if mode not in BAG_MODES:
+        raise ValueError("embedding_bag: mode must be 'sum' or 'mean'")
+    if per_sample_weights is not None:
+        if mode != "sum":
+            raise ValueError("embedding_bag: per_sample_weights go with mode='sum' only")
+        if per_sample_weights.requires_grad:
+            raise ValueError("embedding_bag: per_sample_weights receive no gradient; detach them")
+    opt = table_module.fused_optimizer
+    if opt is not None and getattr(opt, "defer_decay", False) and torch.is_grad_enabled():
+        raise NotImplementedError(
+            "embedding_bag: a deferred-decay Keras Adam replays its rows' decay from "
+            "Embedding.presort, which bags do not support; use defer_decay=False")
+    return _EmbeddingBag.apply(out, table_module.grad_handle, table_module, ids, offsets,
+                               BAG_MODES[mode], valid, per_sample_weights)
+
+
 class _DotInteraction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, self_interaction, skip_gather):

@@ -96,6 +96,13 @@ class SortedIds:
                L.ptr(self.pos), L.ptr(err_flag), L.stream_ptr(ids.device))
         return self
 
+    def remapped(self, pos: torch.Tensor) -> "SortedIds":
+        """This sort with other values in place of its positions (a bag lookup: the bag of each
+        position, functional.BagGrad.remap); the rows are shared."""
+        s = SortedIds.__new__(SortedIds)
+        s.n, s.rows, s.pos, s.n_unique = self.n, self.rows, pos, None
+        return s
+
     @classmethod
     def for_table(cls, table: Embedding, ids: torch.Tensor, ws: L.Workspace | None = None,
                   count_unique: bool = True, valid: torch.Tensor | None = None):
@@ -185,6 +192,20 @@ class SparseOptimizer:
         ids.record_stream(self.side)
         return s
 
+    def apply_bag_async(self, table: Embedding, bag):
+        """A bag lookup's backward (functional.BagGrad) on the side stream: sort with the bag's
+        valid flags, remap the positions to bags, apply. The weighted sum is expanded first."""
+        if id(table) in self._applied:
+            raise RuntimeError("fused sparse optimizer: a table was looked up twice in one step")
+        main = torch.cuda.current_stream(bag.dout.device)
+        L.stream_wait_stream(self.side, main, self._dev_event("apply_in"))
+        with torch.cuda.stream(self.side):
+            self.apply_bag(table, bag, self._params())
+        for t in (bag.ids, bag.offsets, bag.valid, bag.weights, bag.scale, bag.dout):
+            if t is not None:
+                t.record_stream(self.side)
+        self._applied.add(id(table))
+
     def sort_ahead(self, table: Embedding, ids: torch.Tensor) -> SortedIds:
         """Embedding.prefetch: the sort of a later step's ids on a stream of its own (its own
         scratch), so it can run while this step's update still reads the current sort."""
@@ -235,9 +256,13 @@ class SparseOptimizer:
 
     def apply(self, table: Embedding, ids: torch.Tensor, grad_rows: torch.Tensor, params,
               sorted_ids: SortedIds | None = None, row_scale: torch.Tensor | None = None,
-              valid: torch.Tensor | None = None):
+              valid: torch.Tensor | None = None, scale_group: int | None = None):
         """valid (uint8 per id, optional): positions flagged 0 carry no gradient and are left out
-        of the segmented sums (Embedding.take_grad(with_valid=True))."""
+        of the segmented sums (Embedding.take_grad(with_valid=True)).
+        scale_group (with row_scale): the scale of sorted position p is row_scale[p //
+        scale_group], whatever the number of scales — a remapped sort (apply_bag) whose positions
+        are bag indices brings one scale per bag and scale_group = 1. Not given: equal groups of
+        ids.shape[-1] positions per scale, sizes checked."""
         dev = table.weight.device
         s = sorted_ids or SortedIds.for_table(table, ids, self.ws, count_unique=False, valid=valid)
         g = grad_rows.contiguous()
@@ -247,9 +272,12 @@ class SparseOptimizer:
         group = 1
         if row_scale is not None:
             row_scale = row_scale.contiguous()
-            group = ids.shape[-1] if ids.dim() > 1 else s.n // max(row_scale.numel(), 1)
-            if row_scale.numel() * group != s.n:
-                raise ValueError("row_scale must hold one value per example")
+            if scale_group is not None:
+                group = int(scale_group)
+            else:
+                group = ids.shape[-1] if ids.dim() > 1 else s.n // max(row_scale.numel(), 1)
+                if row_scale.numel() * group != s.n:
+                    raise ValueError("row_scale must hold one value per example")
         L.call("rs_embedding_apply_scaled", self.kind, L.ptr(table.weight), L.ptr(m), L.ptr(v),
                table.input_dim, table.output_dim, L.ptr(s.rows), L.ptr(s.pos), s.n, L.ptr(g),
                L.ptr(row_scale), group, params, L.ptr(bitmap), L.ptr(w), w.numel(),
@@ -261,6 +289,43 @@ class SparseOptimizer:
             # the step's rows are now current through it (the catch-up left them one behind)
             L.call("rs_keras_adam_mark", L.ptr(self.last[id(table)]), table.input_dim,
                    L.ptr(s.rows), s.n, self.iterations + 1, L.stream_ptr(dev))
+
+    def _bag_sort(self, table: Embedding, bag) -> SortedIds:
+        so = table.slot_offsets
+        if so is None:
+            return SortedIds.for_table(table, bag.ids, self.ws, count_unique=False,
+                                       valid=bag.valid)
+        # a slab: the sorts take the slot of position p as p % n_slots, a bag's ids belong to slot
+        # bag % n_slots. Index arithmetic to global rows, sorted as one table; ids outside their
+        # slot are dropped through valid, as the sentinel key would drop them
+        dev = bag.ids.device
+        n = bag.ids.numel()
+        slot = bag.remap(torch.arange(n, dtype=torch.int32, device=dev)).long() % table.n_slots
+        lo = so[slot]
+        ids = bag.ids.long()
+        ok = (ids >= 0) & (ids < so[slot + 1] - lo)
+        if bag.valid is not None:
+            ok &= bag.valid != 0
+        rows = torch.where(ok, ids + lo, torch.zeros_like(ids))
+        return SortedIds(rows, table.input_dim, None, table.err_flag, self.ws, count_unique=False,
+                         valid=ok.to(torch.uint8))
+
+    def apply_bag(self, table: Embedding, bag, params):
+        """The backward of a bag lookup (functional.BagGrad) without its [n_ids, dim] gradient:
+        the sorted positions remapped to bag indices read dout [n_bags, dim] in place of the
+        expanded rows, the mean's 1 / count as the row scale. Bit-identical to apply() on
+        bag.expand() (the same sort, the same rounded multiply). The weighted sum expands."""
+        if not bag.remappable:
+            if table.slot_offsets is not None:
+                raise NotImplementedError("a weighted bag sum over a slab table has no backward")
+            ids, rows, valid = bag.expand()
+            return self.apply(table, ids, rows, params, valid=valid)
+        s = self._bag_sort(table, bag)
+        s = s.remapped(bag.remap(s.pos))
+        if bag.n_bags == 0:  # no row of dout to read: an empty gradient (Keras Adam still sweeps)
+            s.n = 0
+        return self.apply(table, bag.ids, bag.dout, params, sorted_ids=s, row_scale=bag.scale,
+                          scale_group=1)
 
     def step(self):
         applied = set()
@@ -274,6 +339,10 @@ class SparseOptimizer:
             applied, self._applied = self._applied, set()
         params = self._params()
         for t in self.tables:
+            bag = t.take_bag_grad()
+            if bag is not None:  # the table's only lookup of the step was a bag: no expansion
+                self.apply_bag(t, bag, params)
+                continue
             got = t.take_grad(with_valid=True)
             if got is None:
                 if (self.kind == L.RS_OPT_KERAS_ADAM and id(t) not in applied
