@@ -1217,15 +1217,17 @@ int32_t rs_tfrecord_parse_criteo(const uint8_t* data, const int64_t* offsets,
                                  int64_t* cat_features, int64_t* label, int32_t* err_flag,
                                  void* stream);
 
-/* ---- the production DLRM training step's top half in one pass (D = 128, <= 27 slots, 13
- * dense inputs, sigmoid head, Keras BCE; ctr/model.py:45-57 + ctr/train.py:77-85) ------------
+/* ---- the production DLRM training step's top half in one pass (D = 128 or 64, at most 27
+ * slots, 13 dense inputs, sigmoid head, Keras BCE; ctr/model.py:45-57 + ctr/train.py:77-85;
+ * anything else is refused with RS_E_INVALID before any launch) ------------------------------
  * Gathers X = [emb(ids), dense], Z = X·Xᵀ, y = σ(Σ q·[Z_strict_upper, dense] + c) (q, c: the
- * composed top MLP, rs_chain3_vec_compose), the BCE loss against label (eps clip, scaled by
- * loss_scale), G_b = y(1-y)·dL/dy, the table gradient rows G_b·(M + Mᵀ)·X_b (M = the
+ * composed top MLP, rs_chain3_vec_compose), the BCE loss against label (eps clip; the loss sum is
+ * the plain Σ_b l_b, NOT scaled by loss_scale, which enters the gradients only),
+ * G_b = y(1-y)·loss_scale·dl_b/dy, the table gradient rows G_b·(M + Mᵀ)·X_b (M = the
  * strict-upper pair weights of q, written unit-scaled: below) in position order, y [B], and the
  * deterministic batch sums (fixed per-wave / per-block / two-level fold order) into
  * sums [rs_dlrm_train_sums()] = A_top [512] (Σ_b row_b·G_b over the compact row, zero padded)
- * | s_top = Σ G | loss sum | A_bot [13][128] = Σ_b x_bᵀ·g_b | s_bot [128] = Σ_b g_b, where
+ * | s_top = Σ G | loss sum | A_bot [13][D] = Σ_b x_bᵀ·g_b | s_bot [D] = Σ_b g_b, where
  * g_b = relu'(dense_b) ⊙ G_b·((M + Mᵀ)·X_b + q_dense)[row S] is the bottom MLP's last-layer
  * gradient and x = xin [B, 13] its input. */
 size_t rs_dlrm_train_workspace_size(int64_t batch);

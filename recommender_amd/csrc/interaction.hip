@@ -1484,6 +1484,9 @@ static int32_t launch_bwd(const Src& src, int64_t batch, int F, int D, InterMode
     const int gw = out_width(F, md.self_interaction, md.skip_gather) + D;
     if (F <= 32 && aligned16 && D == 128 && gw <= 20 * 64) {
       const bool k14 = F <= 28;
+      // <8, 16> is never reached: F >= 29 makes the narrowest row (compact, 29·28/2 + 128 = 534
+      // floats) wider than 8 x 64, so F = 29..32 always takes <20, 16>
+      // (tests/test_dlrm_edges_cpu.py::test_bwd_pipe_instantiations)
       if (gw <= 8 * 64) {
         if (k14) launch_pipe<8, 14>(src, batch, F, md, gout, gstride, gemb, gdense, epw, st);
         else launch_pipe<8, 16>(src, batch, F, md, gout, gstride, gemb, gdense, epw, st);
@@ -1606,6 +1609,7 @@ extern "C" int32_t rs_dlrm_interaction_bwd_rank1(const float* table, int64_t n_r
   GatherSrc src{table, n_rows, ids, id_dtype, n_slots, slot_offsets, dense, nullptr};
   hipStream_t st = as_stream(stream);
   const bool k14 = F <= 28;
+  // <8, 16> is never reached (F >= 29: gw >= 534 > 8 x 64), as in launch_bwd
   if (gw <= 8 * 64) {
     if (k14) launch_pipe<8, 14>(src, batch, F, md, grad_row, width, grad_emb, grad_dense, 0, st, gscale);
     else launch_pipe<8, 16>(src, batch, F, md, grad_row, width, grad_emb, grad_dense, 0, st, gscale);

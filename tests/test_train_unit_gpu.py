@@ -5,12 +5,14 @@ quantities (ctr/model.py:45-57 with the head composed, ctr/layers.py:23-43). Eve
 bounded per element by its magnitude: |got − ref| ≤ 1e-5 · Σ|terms| (the split-bf16 MFMA keeps
 fp32 accuracy relative to that bound). Slot counts on both sides of 16 (the dense
 row then sits in the first or second 16-row block of the Uᵀ product), D 128 / 64, int32 / int64
-ids, out-of-range ids (zero row + flag), a batch that leaves waves empty."""
+ids, out-of-range ids (zero row + flag), a batch that leaves waves empty. The restatement and the
+bound live in tests/dlrm_edges.py, which the edge suite of the same kernels shares."""
 import numpy as np
 import pytest
 import torch
 
 from recommender_amd import _lib as L
+from tests.dlrm_edges import close as _close, reference as _reference
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -52,62 +54,6 @@ def _run(table, ids, offs, dense, xin, label, q, c, S, D):
            L.stream_ptr(table.device))
     torch.cuda.synchronize()
     return y, rows, G, sums, int(err.item())
-
-
-def _reference(table, ids, offs, dense, xin, label, q, c, S, D):
-    """float64: y, G, the unit rows U[b, s] and the batch sums; plus the magnitude bound of each
-    (the same sums over |terms|)."""
-    f = torch.float64
-    B = ids.shape[0]
-    F = S + 1
-    idl = ids.long()
-    lo, hi = offs[:-1][None, :], offs[1:][None, :]
-    ok = (idl >= 0) & (idl < hi - lo)
-    rowi = torch.where(ok, lo + idl, torch.zeros_like(idl))
-    X = torch.cat([table.to(f)[rowi] * ok[..., None], dense.to(f)[:, None, :]], 1)  # [B, F, D]
-    iu = torch.triu_indices(F, F, 1, device=DEV)
-    nz = iu.shape[1]
-    qp, qd = q[:nz].to(f), q[nz:].to(f)
-    Z = X @ X.transpose(1, 2)
-    Zm = (X.abs() @ X.abs().transpose(1, 2))
-    z = Z[:, iu[0], iu[1]]
-    zm = Zm[:, iu[0], iu[1]]
-    h = z @ qp + dense.to(f) @ qd + float(c)
-    hm = zm @ qp.abs() + dense.to(f).abs() @ qd.abs() + abs(float(c))
-    p = torch.sigmoid(h)
-    lb = label.to(f)
-    pc = p.clamp(EPS, 1 - EPS)
-    loss = -(lb * torch.log(pc + EPS) + (1 - lb) * torch.log(1 - pc + EPS))
-    inside = (p >= EPS) & (p <= 1 - EPS)
-    dbce = -(lb / (pc + EPS)) + (1 - lb) / ((1 - pc) + EPS)
-    G = torch.where(inside, dbce / B, torch.zeros_like(p)) * p * (1 - p)
-    M = torch.zeros(F, F, dtype=f, device=DEV)
-    M[iu[0], iu[1]] = qp
-    Sm = M + M.T
-    U = Sm[None] @ X                                      # [B, F, D]
-    Um = Sm.abs()[None] @ X.abs()
-    zrow = torch.cat([z, dense.to(f)], 1)
-    zrm = torch.cat([zm, dense.to(f).abs()], 1)
-    gbot = torch.where(dense > 0, G[:, None] * (U[:, S] + qd[None]), torch.zeros_like(U[:, S]))
-    # error carried into G by h's (|dG/dh| = y(1-y)/B <= 1/(4B)) on top of G's own magnitude
-    gm = G.abs() + hm / (4 * B)
-    gbm = torch.where(dense > 0, gm[:, None] * (Um[:, S] + qd.abs()[None]),
-                      torch.zeros_like(U[:, S]))
-    sums = {"A_top": (zrow * G[:, None]).sum(0), "s_top": G.sum(), "loss": loss.sum(),
-            "A_bot": xin.to(f).T @ gbot, "s_bot": gbot.sum(0)}
-    mags = {"A_top": (zrm * gm[:, None]).sum(0), "s_top": gm.sum(),
-            "loss": (dbce.abs() * 0.25 * hm).sum() + 0.1 * loss.abs().sum(),
-            "A_bot": xin.to(f).abs().T @ gbm, "s_bot": gbm.sum(0)}
-    return p, hm, G, U[:, :S], Um[:, :S], sums, mags, nz, bool((~ok).any())
-
-
-def _close(got, ref, mag, msg, rel=1e-5):
-    got = got.double()
-    tol = rel * mag + 1e-30
-    err = (got - ref).abs()
-    bad = ~(err <= tol)
-    assert not bool(bad.any()), (f"{msg}: {int(bad.sum())} / {bad.numel()} off, max err/tol "
-                                 f"{float((err / tol).max()):.3g}")
 
 
 @pytest.mark.parametrize("B,S,D,id64,oob", [
