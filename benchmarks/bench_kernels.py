@@ -241,6 +241,76 @@ def pinsage_eval(iters, out):
         print(json.dumps(line), flush=True)
 
 
+def topk_ip(iters, out, rounds=5):
+    """Fused top-k inner-product retrieval (rs_topk_ip) against the path it replaces, recommend's
+    chunked torch.matmul (≤ 1 GiB of fp32 scores per chunk) + rs_masked_topk, interleaved in one
+    process: `rounds` rounds of both, each timed with events over its launches; medians reported
+    with every round's time next to them, and the fused call's fraction of the 157.3 TF fp32
+    MFMA peak (2·Q·N·D flop).
+    (a) ML-20M-shaped PinSage: every user's latest item against all items, D 16, k 10, the u2i
+        CSR as the exclusion. (b) EGES-like: 65 536 queries x 2^20 items, D 160, k 10, no
+        exclusion; one launch per round."""
+    from recommender_amd.functional import topk_inner_product
+    from recommender_amd.pinsage import evaluation as E
+    from recommender_amd.pinsage.train import build_dataset
+    from recommender_amd.synthetic import ML20M
+
+    peak_tf = 157.3
+
+    def bench(name, q, x, k, excl_graph, n_iter):
+        Q, N, D = q.shape[0], x.shape[0], x.shape[1]
+        rows = max(32, min(Q, E._SCORE_CHUNK_BYTES // (4 * N)))
+        recs = torch.empty(Q, k, dtype=torch.int32, device=DEV)
+        xt = x.t()
+
+        def base():
+            for b0 in range(0, Q, rows):
+                b1 = min(Q, b0 + rows)
+                recs[b0:b1] = E.masked_topk(torch.matmul(q[b0:b1], xt), k, b0, excl_graph)
+            return recs
+
+        excl = None if excl_graph is None else (excl_graph.u2i_indptr, excl_graph.u2i)
+
+        def fused():
+            return topk_inner_product(q, x, k, exclude=excl, with_scores=False)[0]
+
+        a, b = base().clone(), fused()
+        same = float((a == b).all(1).float().mean())
+        times = {"base": [], "fused": []}
+        s = torch.cuda.current_stream()
+        for _ in range(rounds):
+            for label, fn in (("base", base), ("fused", fused)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record(s)
+                for _ in range(n_iter):
+                    fn()
+                e1.record(s)
+                torch.cuda.synchronize()
+                times[label].append(e0.elapsed_time(e1) / n_iter)
+        mb, mf = float(np.median(times["base"])), float(np.median(times["fused"]))
+        line = {"kernel": "rs_topk_ip vs matmul + rs_masked_topk",
+                "config": {"shape": name, "queries": Q, "items": N, "D": D, "k": k,
+                           "exclusion": excl is not None, "chunk_rows": rows},
+                "base_ms": round(mb, 3), "fused_ms": round(mf, 3), "speedup": round(mb / mf, 2),
+                "fused_frac_of_fp32_mfma_peak": round(2.0 * Q * N * D / (mf * 1e-3) / 1e12 / peak_tf, 4),
+                "rows_identical_to_base": round(same, 5),
+                "base_rounds_ms": [round(t, 3) for t in times["base"]],
+                "fused_rounds_ms": [round(t, 3) for t in times["fused"]]}
+        out.append(line)
+        print(json.dumps(line), flush=True)
+
+    gen = torch.Generator(device=DEV).manual_seed(4)
+    g, _, _ = build_dataset(ML20M, 4, DEV)
+    reprs = torch.randn(g.n_items, 16, device=DEV, generator=gen)
+    latest = E.latest_items(g, "timestamp")
+    bench("pinsage_ml20m", reprs[latest.long()].contiguous(), reprs, 10, g, max(1, iters // 4))
+    del g
+    x = torch.randn(1 << 20, 160, device=DEV, generator=gen)
+    q = x[torch.randint(0, 1 << 20, (65536,), device=DEV, generator=gen)].contiguous()
+    bench("eges_like", q, x, 10, None, 1)
+
+
 def embedding(iters, out):
     from recommender_amd.esmm import FEAT_VOCAB
     from recommender_amd.synthetic import aliccp_batch, scaled_vocab

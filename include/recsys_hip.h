@@ -1120,6 +1120,49 @@ int32_t rs_hit_flags(const int32_t* recs, int64_t n_rows, int32_t k, int64_t use
                      void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Top-k inner-product retrieval over an item catalogue: out[r] = the k items with the highest
+ * queries[r] · items[i], minus a per-query exclusion set, with no [n_queries, n_items] score
+ * matrix. The fused form of recommend's GEMM + rs_masked_topk (pinsage/train/evaluation.py:
+ * 27-51) and the item-to-item recall the EGES hidden vectors exist for (eges/model.py:82-88).
+ *
+ * Score (fixed: results are bit-reproducible). s(r, i) starts at acc = +0.f; for d = 0 … dim-1
+ *   in ascending order acc = fmaf(queries[r*q_ld + d], items[i*i_ld + d], acc) — the chain
+ *   v_mfma_f32_32x32x2_f32 performs. No other rounding; dim is never split across lanes or
+ *   waves. The bits of a score do not depend on which rows share a tile, on n_queries, n_splits
+ *   or k. A chain from +0 can end at -0 (a negative product that underflows), so the zero columns
+ *   the kernel pads dim with are -0 on the query side and +0 on the item side: fmaf(-0, +0, acc)
+ *   leaves every acc as it is, -0 included. Columns [dim, ld) of a row are never read.
+ * Candidates of query r: every item in [0, n_items) except
+ *   - the items in CSR row excl_base + r of excl_indptr (int64) / excl_items (int32). Rows may be
+ *     unsorted and may hold duplicates and ids outside [0, n_items), which are ignored;
+ *     excl_indptr == NULL: no CSR;
+ *   - excl_one[r] when it is >= 0 ("not the query item itself"); excl_one == NULL: none.
+ * Order: score descending, then item ascending; a NaN score ranks as -inf (ties with real -inf
+ *   scores by item) but is written out as the NaN it is; -0 and +0 tie. out_items[r, 0:k] and
+ *   out_scores[r, 0:k] (contiguous [n_queries, k]) are best first; out_scores may be NULL. With
+ *   fewer than k candidates the tail is item -1, score -inf.
+ * Limits: 1 <= k <= 64, 1 <= dim <= 256, q_ld, i_ld >= dim, n_items < 2^31. n_queries == 0 is a
+ *   no-op; n_items == 0 writes all padding. Item rows are read with 16-byte loads when items is
+ *   16-byte aligned and i_ld and dim are multiples of 4, else element by element (same bits,
+ *   several times slower).
+ * n_splits: 0 lets the call choose from the CU count; >= 1 forces that many contiguous item
+ *   ranges of n_items / n_splits items, the last one taking the remainder. One range writes the
+ *   outputs directly; more leave k pairs per (query, range) in the workspace
+ *   (rs_topk_ip_workspace_size with the same four arguments; 0 bytes for one range), which a
+ *   second kernel merges by the same order.
+ * Determinism: the result is a function of the inputs only, whatever order candidates arrive
+ *   in. No block waits for another.
+ * Errors: RS_E_INVALID for null queries / items / out_items, k, dim or ld out of range, a
+ *   negative size, n_items >= 2^31, a workspace that is too small, n_splits < 0 or
+ *   n_splits > n_items when n_items > 0. */
+size_t rs_topk_ip_workspace_size(int32_t n_queries, int64_t n_items, int32_t k, int32_t n_splits);
+int32_t rs_topk_ip(const float* queries, int64_t q_ld, int32_t n_queries, const float* items,
+                   int64_t i_ld, int64_t n_items, int32_t dim, int64_t excl_base,
+                   const int64_t* excl_indptr, const int32_t* excl_items,
+                   const int32_t* excl_one, int32_t k, int32_t n_splits, int32_t* out_items,
+                   float* out_scores, void* workspace, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Ali-CCP and Amazon (DIEN) text → ids (esmm/process_public_dataset.py:40-153,
  * dien/util.py:4-37, dien/data_loader.py:27-63). Lines come from rs_line_index; each line is
  * str.strip()ped as the reference does.

@@ -1,0 +1,546 @@
+// topk_ip.hip — fused top-k inner-product retrieval over an item catalogue (recsys_hip.h,
+// "Top-k inner-product retrieval"): the k best items of every query by q · x, with a per-query
+// exclusion set, without the [n_queries, n_items] score matrix.
+//
+//   topk_ip_kernel   one block = 32 queries × one contiguous item range (a "split"). The query
+//                    tile sits in LDS for the block's life. Each of the 4 waves streams 32-item
+//                    tiles: the tile's rows go global → registers (prefetched one stage ahead) →
+//                    a wave-private LDS stage, 64 columns at a time, and v_mfma_f32_32x32x2_f32
+//                    runs the 32 × 32 scores down the columns in ascending order: per (query,
+//                    item) one accumulator, one fmaf-equivalent step per column, never split.
+//                    A lane then holds 16 queries' scores of one item. A score that beats its
+//                    query's threshold (the k-th best (score, item) kept so far; -inf before k
+//                    are known) is appended to the query's LDS candidate list with an LDS atomic.
+//                    After every round (4 tiles, ≤ 128 appends per query) a list that could
+//                    overflow in the next round (count + 128 > 192) is compacted by one wave:
+//                    exclusion (the CSR row is walked once, 64 ids per load, against the ≤ 192
+//                    candidates in registers), three 64-lane bitonic sorts run side by side, two
+//                    top-64 merges; the best k stay and the threshold is refreshed. Overflow
+//                    cannot happen, so there is no retry. The exclusion test therefore runs only
+//                    on candidates that beat the threshold, a few hundred per query however
+//                    large the range. A compaction is a latency-bound chain of cross-lane
+//                    exchanges that holds its block at the round's barrier: it, not the scoring,
+//                    is what small-dim shapes pay for.
+//   topk_ip_merge    n_splits > 1: every block left its k (item, score) pairs in the workspace;
+//                    one wave per query merges the n_splits sorted lists by the same order.
+//
+// Order: (rank desc, item asc) with rank = the score, NaN ranking as -inf; a total order over
+// distinct items, so the result does not depend on the order candidates arrive in.
+#include <climits>
+
+#include "common.hpp"
+
+namespace rs {
+namespace {
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+constexpr int kTileQ = 32;                  // queries per block (MFMA rows)
+constexpr int kTileI = 32;                  // items per wave tile (MFMA columns)
+constexpr int kIpWaves = 4;
+constexpr int kIpThreads = kIpWaves * kWave;
+constexpr int kRound = kIpWaves * kTileI;   // most appends to one query's list per round
+constexpr int kKMax = 64;
+constexpr int kCap = kKMax + kRound;        // candidate slots per query
+constexpr int kDimMax = 256;
+constexpr int kAutoSplitMax = 64;
+
+struct TopkIpArgs {
+  const float* queries;
+  int64_t q_ld;
+  int32_t n_queries;
+  const float* items;
+  int64_t i_ld;
+  int32_t n_items;
+  int32_t dim;
+  int64_t excl_base;
+  const int64_t* excl_indptr;
+  const int32_t* excl_items;
+  const int32_t* excl_one;
+  int32_t k;
+  int32_t n_splits;
+  int32_t q_tiles;
+  int32_t* out_items;   // n_splits == 1: the outputs; else the workspace lists
+  float* out_scores;    // may be NULL when n_splits == 1
+};
+
+__device__ __forceinline__ float rank_of(float s) { return s != s ? -INFINITY : s; }
+
+// The total order as one integer: a larger key is a better pair. High word: the rank (NaN as
+// -inf, -0 as +0) mapped so that unsigned order is float order; low word: ~item, so the smaller
+// item wins a tie (items are >= 0; the padding item INT_MAX maps lowest). One 64-bit compare
+// and no branch per exchange of the sorts.
+__device__ __forceinline__ uint64_t order_key(float s, int32_t ix) {
+  const uint32_t b = __float_as_uint(rank_of(s) + 0.f);
+  const uint32_t u = b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
+  return ((uint64_t)u << 32) | (uint32_t)~ix;
+}
+
+__device__ __forceinline__ bool better(float a, int32_t ia, float b, int32_t ib) {
+  return order_key(a, ia) > order_key(b, ib);
+}
+
+// N independent bitonic sorts of one (score, item) per lane across the wave, best first; the N
+// lists advance step by step together, so their cross-lane exchanges overlap
+template <int N>
+__device__ __forceinline__ void wave_sort(float (&v)[N], int32_t (&ix)[N], int lane) {
+#pragma unroll
+  for (int k = 2; k <= kWave; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const bool keep_better = ((lane & k) == 0) == ((lane & j) == 0);
+#pragma unroll
+      for (int c = 0; c < N; ++c) {
+        const float ov = __shfl_xor(v[c], j, kWave);
+        const int32_t oi = __shfl_xor(ix[c], j, kWave);
+        const uint64_t mine = order_key(v[c], ix[c]), theirs = order_key(ov, oi);
+        const bool take = keep_better ? theirs > mine : mine > theirs;
+        v[c] = take ? ov : v[c];
+        ix[c] = take ? oi : ix[c];
+      }
+    }
+  }
+}
+
+// (v, ix) and (bv, bi) both sorted best first across the wave → (v, ix) = the best 64 of the
+// 128, sorted: lane l keeps the better of a[l] and b[63 - l] (a bitonic sequence holding the
+// best 64), then one bitonic merge.
+__device__ __forceinline__ void wave_merge_top(float& v, int32_t& ix, float bv, int32_t bi,
+                                               int lane) {
+  const float rv = __shfl(bv, kWave - 1 - lane, kWave);
+  const int32_t ri = __shfl(bi, kWave - 1 - lane, kWave);
+  const bool first = order_key(rv, ri) > order_key(v, ix);
+  v = first ? rv : v;
+  ix = first ? ri : ix;
+#pragma unroll
+  for (int j = kWave >> 1; j > 0; j >>= 1) {
+    const float ov = __shfl_xor(v, j, kWave);
+    const int32_t oi = __shfl_xor(ix, j, kWave);
+    const uint64_t mine = order_key(v, ix), theirs = order_key(ov, oi);
+    const bool take = (lane & j) == 0 ? theirs > mine : mine > theirs;
+    v = take ? ov : v;
+    ix = take ? oi : ix;
+  }
+}
+
+// One wave reduces query row q's candidate list to its best k non-excluded entries (sorted, at
+// slots [0, k)), sets its count and, once k are known, its threshold. out_i != nullptr: also
+// writes the k entries (best first) to out_i / out_s (out_s may be NULL); `final` turns the
+// padding (INT_MAX, -inf) into (-1, -inf).
+__device__ __forceinline__ void compact_query(int q, int lane, int32_t k, float* cand_s,
+                                              int32_t* cand_i, int32_t* cnt, float* th_s,
+                                              int32_t* th_i, const int64_t* excl_indptr,
+                                              const int32_t* excl_items, int64_t excl_row,
+                                              int32_t* out_i, float* out_s, bool final) {
+  float* cs = cand_s + q * kCap;
+  int32_t* ci = cand_i + q * kCap;
+  const int32_t n = min(__builtin_amdgcn_readfirstlane(cnt[q]), kCap);
+  constexpr int NC = kCap / kWave;
+  float v[NC];
+  int32_t ix[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int idx = c * kWave + lane;
+    v[c] = idx < n ? cs[idx] : -INFINITY;
+    ix[c] = idx < n ? ci[idx] : INT_MAX;
+  }
+  if (excl_indptr && n > 0) {
+    const int64_t lo = excl_indptr[excl_row], hi = excl_indptr[excl_row + 1];
+    const int32_t* row = excl_items + lo;
+    const int64_t len64 = hi > lo ? hi - lo : 0;
+    const int32_t len =
+        __builtin_amdgcn_readfirstlane(len64 < INT_MAX ? (int32_t)len64 : INT_MAX);
+    bool hit[NC] = {};
+    for (int32_t e = 0; e < len; e += kWave) {
+      const int32_t x = e + lane < len ? row[e + lane] : -1;  // -1 matches no candidate
+      const int32_t m = min(kWave, len - e);
+      for (int32_t t = 0; t < m; ++t) {
+        const int32_t y = __builtin_amdgcn_readlane(x, t);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) hit[c] |= ix[c] == y;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      if (hit[c]) {
+        v[c] = -INFINITY;
+        ix[c] = INT_MAX;
+      }
+  }
+  wave_sort<NC>(v, ix, lane);
+#pragma unroll
+  for (int c = 1; c < NC; ++c)
+    if (n > c * kWave) wave_merge_top(v[0], ix[0], v[c], ix[c], lane);
+  const bool keep = lane < k && ix[0] != INT_MAX;  // the padding sorts last: a prefix
+  const int32_t nk = __popcll(__ballot(keep));
+  const float kv = __shfl(v[0], k - 1, kWave);
+  const int32_t ki = __shfl(ix[0], k - 1, kWave);
+  __builtin_amdgcn_wave_barrier();  // every lane's reads of the list are done
+  if (lane < k) {
+    cs[lane] = v[0];
+    ci[lane] = ix[0];
+  }
+  if (lane == 0) {
+    cnt[q] = nk;
+    if (nk >= k) {
+      th_s[q] = kv;
+      th_i[q] = ki;
+    }
+  }
+  if (out_i && lane < k) {
+    const bool pad = ix[0] == INT_MAX;
+    out_i[lane] = pad && final ? -1 : ix[0];
+    if (out_s) out_s[lane] = pad ? -INFINITY : v[0];
+  }
+}
+
+// W = 4 << LOGW4 columns are staged at a time (the power of two ≥ dim, at most 64).
+template <int LOGW4, bool FAST>
+__global__ __launch_bounds__(kIpThreads) void topk_ip_kernel(const TopkIpArgs a) {
+  constexpr int W = 4 << LOGW4;
+  constexpr int W4 = 1 << LOGW4;  // float4 slots per staged row
+  constexpr int SS = W + 1;       // odd row strides: the 32 rows of a column fall in 32 banks
+  constexpr int NSLOT = (kTileI * W4 + kWave - 1) / kWave;
+  extern __shared__ __align__(16) float lds[];  // every sub-array below starts 128-byte aligned
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int32_t dim = a.dim;
+  constexpr int G = W / 2 < 8 ? W / 2 : 8;  // MFMA steps per operand group
+  constexpr int GC = 2 * G;                 // = ip_group_cols(W)
+  const int dq = (dim + GC - 1) / GC * GC;
+  const int QS = dq + 1;
+  float* Qs = lds;
+  float* st = Qs + kTileQ * QS + wid * (kTileI * SS);
+  float* cand_s = Qs + kTileQ * QS + kIpWaves * kTileI * SS;
+  int32_t* cand_i = reinterpret_cast<int32_t*>(cand_s + kTileQ * kCap);
+  int32_t* cnt = cand_i + kTileQ * kCap;
+  float* th_s = reinterpret_cast<float*>(cnt + kTileQ);
+  int32_t* th_i = reinterpret_cast<int32_t*>(th_s + kTileQ);
+  int32_t* ex1 = th_i + kTileQ;
+
+  const int32_t sp = blockIdx.x / a.q_tiles;
+  const int32_t q0 = (blockIdx.x - sp * a.q_tiles) * kTileQ;
+  const int32_t nq = min(kTileQ, a.n_queries - q0);
+  const int32_t per = a.n_items / a.n_splits;
+  const int32_t lo = sp * per;
+  const int32_t hi = sp == a.n_splits - 1 ? a.n_items : lo + per;
+
+  // The pad column of an odd dim holds -0 (the staged items' holds +0): the padded step adds a
+  // -0 product, the identity for every acc, a -0 included (which a negative product that
+  // underflows leaves; +0 there would turn it into +0).
+  for (int e = tid; e < kTileQ * dq; e += kIpThreads) {
+    const int row = e / dq, col = e - row * dq;
+    const float pad = col < dim ? 0.f : -0.f;
+    Qs[row * QS + col] =
+        row < nq && col < dim ? a.queries[(int64_t)(q0 + row) * a.q_ld + col] : pad;
+  }
+  if (tid < kTileQ) {
+    cnt[tid] = 0;
+    th_s[tid] = tid < nq ? -INFINITY : INFINITY;  // rows past the last query take nothing
+    th_i[tid] = INT_MAX;
+    ex1[tid] = a.excl_one && tid < nq ? a.excl_one[q0 + tid] : -1;
+  }
+  __syncthreads();
+
+  const int32_t n_tiles = (hi - lo + kTileI - 1) / kTileI;
+  const int32_t n_rounds = (n_tiles + kIpWaves - 1) / kIpWaves;
+  const int32_t n_chunks = (dim + W - 1) / W;
+
+  // This lane's float4 slots of columns [c0, c0 + W) of the tile at item jb.
+  // FAST (items 16-byte aligned, i_ld and dim multiples of 4): unconditional loads and nothing
+  // that reads them, so all are in flight together and stay so until stage() (a select or a
+  // branch on the way made the compiler wait for each load before issuing the next). A row
+  // past the range's end re-reads the last row (its scores are never looked at), a slot past
+  // dim the row's last four columns (stage() zeroes it).
+  // Otherwise: guarded element loads, zeros past the range's end and past dim.
+  float4 pre[NSLOT];
+  auto fetch = [&](int64_t jb, int32_t c0) {
+#pragma unroll
+    for (int t = 0; t < NSLOT; ++t) {
+      const int slot = lane + kWave * t;
+      const int row = (slot >> LOGW4) & (kTileI - 1), col = c0 + 4 * (slot & (W4 - 1));
+      const int64_t j = jb + row;
+      if constexpr (FAST) {
+        const int64_t jc = j < hi ? j : (int64_t)hi - 1;
+        pre[t] = *reinterpret_cast<const float4*>(a.items + jc * a.i_ld + min(col, dim - 4));
+      } else {
+        float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (j < hi && col < dim) {
+          const float* p = a.items + j * a.i_ld + col;
+          x.x = p[0];
+          if (col + 1 < dim) x.y = p[1];
+          if (col + 2 < dim) x.z = p[2];
+          if (col + 3 < dim) x.w = p[3];
+        }
+        pre[t] = x;
+      }
+    }
+  };
+  auto stage = [&](int32_t c0) {
+#pragma unroll
+    for (int t = 0; t < NSLOT; ++t) {
+      const int slot = lane + kWave * t;
+      if (slot < kTileI * W4) {
+        float* d = st + (slot >> LOGW4) * SS + 4 * (slot & (W4 - 1));
+        const bool ok = c0 + 4 * (slot & (W4 - 1)) < dim;
+        d[0] = ok ? pre[t].x : 0.f;
+        d[1] = ok ? pre[t].y : 0.f;
+        d[2] = ok ? pre[t].z : 0.f;
+        d[3] = ok ? pre[t].w : 0.f;
+      }
+    }
+  };
+
+  const int mrow = lane & 31, half = lane >> 5;
+  fetch((int64_t)lo + wid * kTileI, 0);
+  for (int32_t round = 0; round < n_rounds; ++round) {
+    const int64_t jb64 = (int64_t)lo + ((int64_t)round * kIpWaves + wid) * kTileI;
+    const bool active = jb64 < hi;
+    const int32_t jb = active ? (int32_t)jb64 : hi;
+    f32x16 acc = {};
+    for (int32_t c = 0; c < n_chunks; ++c) {
+      stage(c * W);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      {  // the next stage's rows are in flight while this one multiplies (past the last tile:
+         // the range's last row again, or nothing, never used)
+        const bool last = c + 1 == n_chunks;
+        fetch(last ? jb64 + kRound : jb64, last ? 0 : (c + 1) * W);
+      }
+      if (active) {
+        const int c0 = c * W;
+        const float* qa = Qs + mrow * QS + c0 + half;
+        const float* xb = st + mrow * SS + half;
+        // G steps (GC columns) at a time, the next group's operands read while this one
+        // multiplies; the columns past dim hold -0 (queries) and +0 (items): identity steps
+        const int groups = (min(W, dim - c0) + GC - 1) / GC;
+        float fa[G], fb[G];
+#pragma unroll
+        for (int s = 0; s < G; ++s) {
+          fa[s] = qa[2 * s];
+          fb[s] = xb[2 * s];
+        }
+        for (int g = 0; g < groups; ++g) {
+          const int nx = (g + 1 < groups ? g + 1 : g) * GC;  // the last group is read twice
+          float na[G], nfb[G];
+#pragma unroll
+          for (int s = 0; s < G; ++s) {
+            na[s] = qa[nx + 2 * s];
+            nfb[s] = xb[nx + 2 * s];
+          }
+#pragma unroll
+          for (int s = 0; s < G; ++s)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[s], fb[s], acc, 0, 0, 0);
+#pragma unroll
+          for (int s = 0; s < G; ++s) {
+            fa[s] = na[s];
+            fb[s] = nfb[s];
+          }
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+    if (active && jb + mrow < hi) {
+      const int32_t j = jb + mrow;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float4 t4 = *reinterpret_cast<const float4*>(th_s + 8 * g + 4 * half);
+        const float th[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int i = 8 * g + 4 * half + u;  // the query row of accumulator register 4 g + u
+          const float s = acc[4 * g + u];
+          if (s < th[u]) continue;  // nearly every pair; false for a NaN on either side
+          if (i < nq && better(s, j, th[u], th_i[i]) && j != ex1[i]) {
+            const int32_t slot = atomicAdd(&cnt[i], 1);
+            if (slot < kCap) {  // always: a list enters a round with count + kRound <= kCap
+              cand_s[i * kCap + slot] = s;
+              cand_i[i * kCap + slot] = j;
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    const uint64_t full = __ballot(lane < nq && cnt[lane & (kTileQ - 1)] + kRound > kCap);
+    for (int q = wid; q < nq; q += kIpWaves)
+      if ((full >> q) & 1)
+        compact_query(q, lane, a.k, cand_s, cand_i, cnt, th_s, th_i, a.excl_indptr,
+                      a.excl_items, a.excl_base + q0 + q, nullptr, nullptr, false);
+    __syncthreads();
+  }
+  const bool final = a.n_splits == 1;
+  for (int q = wid; q < nq; q += kIpWaves) {
+    const int64_t o = ((int64_t)(q0 + q) * a.n_splits + sp) * a.k;
+    compact_query(q, lane, a.k, cand_s, cand_i, cnt, th_s, th_i, a.excl_indptr, a.excl_items,
+                  a.excl_base + q0 + q, a.out_items + o, a.out_scores ? a.out_scores + o : nullptr,
+                  final);
+  }
+}
+
+// one wave per query: the n_splits sorted lists of k → the best k
+__global__ __launch_bounds__(kIpThreads) void topk_ip_merge_kernel(
+    const int32_t* __restrict__ ws_items, const float* __restrict__ ws_scores, int32_t n_queries,
+    int32_t n_splits, int32_t k, int32_t* __restrict__ out_items, float* __restrict__ out_scores) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * kIpWaves + (threadIdx.x >> 6);
+  if (r >= n_queries) return;
+  float v = -INFINITY;
+  int32_t ix = INT_MAX;
+  for (int32_t sp = 0; sp < n_splits; ++sp) {
+    const int64_t o = (r * n_splits + sp) * k + lane;
+    const float bv = lane < k ? ws_scores[o] : -INFINITY;
+    const int32_t bi = lane < k ? ws_items[o] : INT_MAX;
+    wave_merge_top(v, ix, bv, bi, lane);
+  }
+  if (lane < k) {
+    const bool pad = ix == INT_MAX;
+    out_items[r * k + lane] = pad ? -1 : ix;
+    if (out_scores) out_scores[r * k + lane] = pad ? -INFINITY : v;
+  }
+}
+
+__global__ __launch_bounds__(256) void topk_ip_pad_kernel(int64_t n, int32_t* __restrict__ items,
+                                                          float* __restrict__ scores) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  items[i] = -1;
+  if (scores) scores[i] = -INFINITY;
+}
+
+int ip_group_cols(int W) { return W < 16 ? W : 16; }
+
+size_t ip_lds_bytes(int32_t dim, int W) {
+  const int gc = ip_group_cols(W);
+  const int dq = (dim + gc - 1) / gc * gc;
+  return sizeof(float) * ((size_t)kTileQ * (dq + 1) + (size_t)kIpWaves * kTileI * (W + 1) +
+                          (size_t)kTileQ * kCap * 2 + (size_t)kTileQ * 4);
+}
+
+int cu_count() {
+  static const int n = [] {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus <= 0) {
+      (void)hipGetLastError();
+      return 256;
+    }
+    return cus;
+  }();
+  return n;
+}
+
+// the item ranges of a call: the forced count, or enough blocks for two per CU with ranges of
+// at least 1024 items
+int64_t pick_splits(int32_t n_queries, int64_t n_items, int32_t n_splits) {
+  if (n_splits > 0) return n_splits;
+  if (n_queries <= 0 || n_items <= 0) return 1;
+  const int64_t q_tiles = ceil_div(n_queries, kTileQ);
+  int64_t s = ceil_div(2 * (int64_t)cu_count(), q_tiles);
+  s = s < n_items / 1024 ? s : n_items / 1024;
+  s = s < kAutoSplitMax ? s : kAutoSplitMax;
+  return s < 1 ? 1 : s;
+}
+
+size_t ws_bytes_for(int32_t n_queries, int64_t splits, int32_t k) {
+  if (splits <= 1 || n_queries <= 0) return 0;
+  return 2 * align_up((size_t)n_queries * (size_t)splits * (size_t)k * 4, 256);
+}
+
+template <int LOGW4, bool FAST>
+int32_t launch_topk_ip_as(const TopkIpArgs& a, hipStream_t st) {
+  const size_t lds = ip_lds_bytes(a.dim, 4 << LOGW4);
+  if (lds > 48 * 1024)
+    RS_CHECK_HIP(hipFuncSetAttribute((const void*)topk_ip_kernel<LOGW4, FAST>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  topk_ip_kernel<LOGW4, FAST>
+      <<<(unsigned)((int64_t)a.q_tiles * a.n_splits), kIpThreads, lds, st>>>(a);
+  RS_CHECK_LAUNCH();
+  return RS_OK;
+}
+
+template <int LOGW4>
+int32_t launch_topk_ip(const TopkIpArgs& a, hipStream_t st) {
+  const bool fast = (a.i_ld & 3) == 0 && (a.dim & 3) == 0 &&
+                    (reinterpret_cast<uintptr_t>(a.items) & 15) == 0;
+  return fast ? launch_topk_ip_as<LOGW4, true>(a, st) : launch_topk_ip_as<LOGW4, false>(a, st);
+}
+
+}  // namespace
+}  // namespace rs
+
+using namespace rs;
+
+extern "C" size_t rs_topk_ip_workspace_size(int32_t n_queries, int64_t n_items, int32_t k,
+                                            int32_t n_splits) {
+  if (n_queries <= 0 || n_items <= 0 || k <= 0 || n_splits < 0) return 0;
+  return ws_bytes_for(n_queries, pick_splits(n_queries, n_items, n_splits), k);
+}
+
+extern "C" int32_t rs_topk_ip(const float* queries, int64_t q_ld, int32_t n_queries,
+                              const float* items, int64_t i_ld, int64_t n_items, int32_t dim,
+                              int64_t excl_base, const int64_t* excl_indptr,
+                              const int32_t* excl_items, const int32_t* excl_one, int32_t k,
+                              int32_t n_splits, int32_t* out_items, float* out_scores,
+                              void* workspace, size_t ws_bytes, void* stream) {
+  RS_CHECK_ARG(k >= 1 && k <= kKMax, "rs_topk_ip: need 1 <= k <= 64, got %d", k);
+  RS_CHECK_ARG(dim >= 1 && dim <= kDimMax, "rs_topk_ip: need 1 <= dim <= 256, got %d", dim);
+  RS_CHECK_ARG(q_ld >= dim && i_ld >= dim, "rs_topk_ip: q_ld and i_ld must be >= dim");
+  RS_CHECK_ARG(n_queries >= 0 && n_items >= 0 && n_items < ((int64_t)1 << 31),
+               "rs_topk_ip: need n_queries >= 0 and 0 <= n_items < 2^31");
+  RS_CHECK_ARG(n_splits >= 0 && (n_items == 0 || n_splits <= n_items),
+               "rs_topk_ip: need 0 <= n_splits <= n_items");
+  RS_CHECK_ARG(excl_base >= 0, "rs_topk_ip: excl_base < 0");
+  if (n_queries == 0) return RS_OK;
+  RS_CHECK_ARG(out_items != nullptr, "rs_topk_ip: out_items is NULL");
+  hipStream_t st = as_stream(stream);
+  if (n_items == 0) {
+    const int64_t n = (int64_t)n_queries * k;
+    topk_ip_pad_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(n, out_items, out_scores);
+    RS_CHECK_LAUNCH();
+    return RS_OK;
+  }
+  RS_CHECK_ARG(queries != nullptr && items != nullptr, "rs_topk_ip: queries / items is NULL");
+  const int64_t splits = pick_splits(n_queries, n_items, n_splits);
+  const int64_t q_tiles = ceil_div(n_queries, kTileQ);
+  RS_CHECK_ARG(q_tiles * splits < ((int64_t)1 << 31), "rs_topk_ip: too many blocks");
+  const size_t need = ws_bytes_for(n_queries, splits, k);
+  RS_CHECK_ARG(need == 0 || (workspace != nullptr && ws_bytes >= need),
+               "rs_topk_ip: workspace of %zu bytes, need %zu", ws_bytes, need);
+  TopkIpArgs a;
+  a.queries = queries;
+  a.q_ld = q_ld;
+  a.n_queries = n_queries;
+  a.items = items;
+  a.i_ld = i_ld;
+  a.n_items = (int32_t)n_items;
+  a.dim = dim;
+  a.excl_base = excl_base;
+  a.excl_indptr = excl_indptr;
+  a.excl_items = excl_items;
+  a.excl_one = excl_one;
+  a.k = k;
+  a.n_splits = (int32_t)splits;
+  a.q_tiles = (int32_t)q_tiles;
+  int32_t* ws_items = static_cast<int32_t*>(workspace);
+  float* ws_scores = reinterpret_cast<float*>(static_cast<char*>(workspace) + need / 2);
+  a.out_items = splits == 1 ? out_items : ws_items;
+  a.out_scores = splits == 1 ? out_scores : ws_scores;
+  int32_t rc;
+  if (dim <= 4)
+    rc = launch_topk_ip<0>(a, st);
+  else if (dim <= 8)
+    rc = launch_topk_ip<1>(a, st);
+  else if (dim <= 16)
+    rc = launch_topk_ip<2>(a, st);
+  else if (dim <= 32)
+    rc = launch_topk_ip<3>(a, st);
+  else
+    rc = launch_topk_ip<4>(a, st);
+  if (rc != RS_OK || splits == 1) return rc;
+  topk_ip_merge_kernel<<<(unsigned)ceil_div(n_queries, kIpWaves), kIpThreads, 0, st>>>(
+      ws_items, ws_scores, n_queries, (int32_t)splits, k, out_items, out_scores);
+  RS_CHECK_LAUNCH();
+  return RS_OK;
+}

@@ -1,0 +1,40 @@
+"""Item-to-item recall over the EGES hidden vectors (what eges/model.py:82-88 get_hidden exists
+for): every item's vector, then the k nearest items by inner product through rs_topk_ip.
+
+item_hidden    [n_items, D]: model.get_hidden over every item id, in chunks, without gradients.
+               GES / EGES take the items' category and brand ids; DeepWalk takes ids only.
+similar_items  (idx int32 [Q, k], scores fp32 [Q, k]): per query item its k best other items
+               (the query item itself is excluded). Inner product: normalise the rows first for
+               cosine similarity.
+"""
+from __future__ import annotations
+
+import torch
+
+from ..functional import topk_inner_product
+from .model import DeepWalk
+
+
+def item_hidden(model, item2cat=None, item2brand=None, batch: int = 65536) -> torch.Tensor:
+    table = model.input_embedding if isinstance(model, DeepWalk) else model.id_embedding
+    n, dev = table.input_dim, table.weight.device
+    side = None
+    if not isinstance(model, DeepWalk):
+        if item2cat is None or item2brand is None:
+            raise ValueError("item_hidden: GES / EGES need item2cat and item2brand")
+        side = [torch.as_tensor(t).to(dev, torch.int32).reshape(-1, 1) for t in (item2cat, item2brand)]
+        if any(t.shape[0] != n for t in side):
+            raise ValueError(f"item_hidden: item2cat and item2brand must hold {n} ids")
+    out = torch.empty(n, table.output_dim, device=dev)
+    with torch.no_grad():
+        for b0 in range(0, n, max(int(batch), 1)):
+            b1 = min(n, b0 + max(int(batch), 1))
+            ids = torch.arange(b0, b1, dtype=torch.int32, device=dev).reshape(-1, 1)
+            inp = ids if side is None else (ids, side[0][b0:b1], side[1][b0:b1])
+            out[b0:b1] = model.get_hidden(inp).reshape(b1 - b0, -1)
+    return out
+
+
+def similar_items(hidden: torch.Tensor, query_items: torch.Tensor, k: int):
+    query_items = torch.as_tensor(query_items).to(hidden.device)
+    return topk_inner_product(hidden[query_items.long()], hidden, k, exclude_one=query_items)

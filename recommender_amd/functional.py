@@ -744,3 +744,56 @@ _APPLY_EARLY = os.environ.get("RS_APPLY_EARLY", "1") == "1"
 def _train_ws(B, dev):
     """The train kernel's cached workspace (its per-block partial sums stay there after a step)."""
     return L.workspace("dlrm.train", L.lib().rs_dlrm_train_workspace_size(B), dev)
+
+
+def _row_major(t: torch.Tensor, name: str):
+    """(fp32 tensor, row stride in floats) of a 2-D device tensor: a row-strided view (a column
+    block of a wider matrix) is taken as it is, anything else is made contiguous."""
+    L.require_device(t, name)
+    if t.dim() != 2:
+        raise ValueError(f"topk_inner_product: {name} must be 2-D, got shape {tuple(t.shape)}")
+    t = t.detach().float()
+    if t.shape[0] > 1 and t.shape[1] > 0 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+        return t, t.stride(0)
+    t = t.contiguous()
+    return t, max(t.shape[1], 1)
+
+
+def topk_inner_product(queries, items, k: int, exclude=None, exclude_base: int = 0,
+                       exclude_one=None, with_scores: bool = True, n_splits: int = 0):
+    """(idx int32 [Q, k], scores fp32 [Q, k]): per query row the k items with the highest inner
+    product, best first (score desc, item asc; padding -1 / -inf), by rs_topk_ip: no [Q, n_items]
+    score matrix. exclude: (indptr int64 [>= exclude_base + Q + 1], indices int32) CSR, row
+    exclude_base + r lists the items query r must not get; exclude_one: int32 [Q], one more such
+    item per query (< 0: none). with_scores=False returns (idx, None). n_splits: 0 = chosen from
+    the CU count, >= 1 forces that many item ranges. No autograd."""
+    q, q_ld = _row_major(queries, "queries")
+    x, i_ld = _row_major(items, "items")
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"topk_inner_product: queries are {q.shape[1]} wide, items {x.shape[1]}")
+    if q.device != x.device:
+        raise ValueError("topk_inner_product: queries and items on different devices")
+    dev = q.device
+    Q, dim = q.shape
+    n_items = x.shape[0]
+    ip = it = one = None
+    if exclude is not None:
+        ip, it = exclude
+        L.require_device(ip, "exclude indptr")
+        L.require_device(it, "exclude indices")
+        ip, it = ip.to(torch.int64).contiguous(), it.to(torch.int32).contiguous()
+        if ip.numel() < exclude_base + Q + 1:
+            raise ValueError("topk_inner_product: exclude indptr shorter than exclude_base + Q + 1")
+    if exclude_one is not None:
+        L.require_device(exclude_one, "exclude_one")
+        one = exclude_one.to(torch.int32).contiguous()
+        if one.numel() != Q:
+            raise ValueError("topk_inner_product: exclude_one must hold one id per query")
+    idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    val = torch.empty(Q, k, device=dev) if with_scores else None
+    need = L.lib().rs_topk_ip_workspace_size(Q, n_items, k, n_splits)
+    ws = L.workspace("functional.topk_ip", need, dev) if need else None
+    L.call("rs_topk_ip", L.ptr(q), q_ld, Q, L.ptr(x), i_ld, n_items, dim, exclude_base,
+           L.ptr(ip), L.ptr(it), L.ptr(one), k, n_splits, L.ptr(idx), L.ptr(val), L.ptr(ws),
+           ws.numel() if ws is not None else 0, L.stream_ptr(dev))
+    return idx, val

@@ -10,6 +10,10 @@ recommend        evaluation.py:27-51  latest item per user (rs_latest_item) → 
                  items set to -inf and top-k (rs_masked_topk). Returns [n_users, top_k] int32
                  on the device, best first (the reference's argpartition gives the same set
                  in no order). batch_size only sizes the chunks; it does not change results.
+                 fused=True: one rs_topk_ip call (functional.topk_inner_product) on the latest
+                 items' rows with the u2i CSR as the exclusion: no score matrix, no
+                 n_items ≤ 2^20 limit; scores are the ascending fmaf chain, so a near-tie may
+                 rank differently than under the GEMM's rounding.
 hit_rate_eval    evaluation.py:54-65  mean over users of any(recommended ∈ ground truth).
 train_test_split_by_time / build_val_test_matrix   util.py:5-39 (numpy instead of pandas:
                  per user by time, the last rating → test and the second-to-last → val;
@@ -104,11 +108,17 @@ def masked_topk(scores: torch.Tensor, top_k: int, user_base: int = 0,
 
 def recommend(full_graph: HeteroGraph, top_k: int, item_reprs: torch.Tensor,
               user2item_etype=None, utype=None, timestamp: str = "timestamp",
-              batch_size: int = 32):
+              batch_size: int = 32, fused: bool = False):
     L.require_device(item_reprs, "item_reprs")
     reprs = item_reprs.float().contiguous()
     n_users, n_items = full_graph.n_users, reprs.shape[0]
     latest = latest_items(full_graph, timestamp)
+    if fused:
+        from ..functional import topk_inner_product
+
+        return topk_inner_product(reprs[latest.long()], reprs, top_k,
+                                  exclude=(full_graph.u2i_indptr, full_graph.u2i),
+                                  with_scores=False)[0]
     rows = max(batch_size, min(n_users, _SCORE_CHUNK_BYTES // (4 * n_items)))
     recs = torch.empty(n_users, top_k, dtype=torch.int32, device=reprs.device)
     for b0 in range(0, n_users, rows):

@@ -28,7 +28,8 @@ what the trained model's own Convolve computes with every item in one batch (it 
 under that global norm, layers.py:28-29); None leaves fc_2's output as it is.
 
 `python -m recommender_amd.pinsage.inference [--graph ml1m|ml20m] [--out reprs.npy]` runs it on
-the synthetic MovieLens graph of pinsage/train.py.
+the synthetic MovieLens graph of pinsage/train.py; `--neighbors K --neighbors-out nbrs.npy` adds
+each item's K nearest items by inner product (rs_topk_ip, the item itself excluded).
 """
 from __future__ import annotations
 
@@ -214,7 +215,14 @@ def main(argv=None):
     ap.add_argument("--norm", choices=["row", "frobenius", "none"], default="row")
     ap.add_argument("--fused", type=int, default=1, help="0: compose the existing kernels")
     ap.add_argument("--out", default=None, help="write the representations to this .npy file")
+    ap.add_argument("--neighbors", type=int, default=0, metavar="K",
+                    help="with --neighbors-out: each item's K nearest items by inner product")
+    ap.add_argument("--neighbors-out", default=None, metavar="FILE",
+                    help="write the [n_items, K] int32 neighbour ids (best first, the item "
+                         "itself excluded, -1 = none left) to this .npy file")
     args = ap.parse_args(argv)
+    if bool(args.neighbors) != bool(args.neighbors_out):
+        ap.error("--neighbors K and --neighbors-out FILE go together")
     torch.manual_seed(args.seed)
     g, _, _ = build_dataset(ML1M if args.graph == "ml1m" else ML20M, args.seed)
     model = PinSageModel(g, g.itype, 2, 8, 32, 16)
@@ -231,6 +239,16 @@ def main(argv=None):
 
         np.save(args.out, reprs.cpu().numpy())
         print(f"wrote {args.out}")
+    if args.neighbors_out:
+        import numpy as np
+
+        from ..functional import topk_inner_product
+
+        own = torch.arange(reprs.shape[0], dtype=torch.int32, device=reprs.device)
+        nbrs, _ = topk_inner_product(reprs, reprs, args.neighbors, exclude_one=own,
+                                     with_scores=False)
+        np.save(args.neighbors_out, nbrs.cpu().numpy())
+        print(f"wrote {args.neighbors_out}")
     return reprs
 
 
