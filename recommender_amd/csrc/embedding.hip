@@ -680,19 +680,30 @@ __global__ __launch_bounds__(256) void seg_tile32_kernel(const uint32_t* __restr
 // (chunk[t][1], tile flag bit 0) and, at a group's first tile, the continuation's group sum
 // (chunk[t][0]); seg_fixup_kernel folds those (level 2). Bit-identical to seg_tile32 + seg_chunk
 // + seg_fixup, one launch fewer and no global partials.
-template <int OPT, int Q = 0>
-__global__ __launch_bounds__(1024) void seg_group32_kernel(const uint32_t* __restrict__ keys,
-                                                           const int32_t* __restrict__ pos,
-                                                           int64_t n, uint32_t n_rows,
-                                                           const float* __restrict__ grad,
-                                                           ApplyArgs a, int64_t n_tiles) {
+//
+// Block shape: HW half-waves (HW * 32 threads, HW = 32 / 16 / 8) walk the group's 32 tiles in
+// 32 / HW rounds, half-wave gi taking tiles gi, gi + HW, ... one after another (strided, not
+// adjacent: in each round the block reads HW consecutive tiles of keys and positions, and a last
+// group with few tiles spreads them over all half-waves instead of the first few). The walk
+// keeps its 128 VGPRs (4 waves per SIMD) at every shape, so a CU holds 32 / HW blocks and a
+// foreign block that lands on it displaces HW half-waves of the walk, not all 32. Each tile's
+// edges (Tile32Edges) go to LDS beside its partials; after the barrier a half-wave folds for the
+// tiles it walked, in tile order: the same additions in the same order at every HW.
+template <int OPT, int Q = 0, int HW = 32>
+__global__ __launch_bounds__(HW * 32, 4) void seg_group32_kernel(const uint32_t* __restrict__ keys,
+                                                                 const int32_t* __restrict__ pos,
+                                                                 int64_t n, uint32_t n_rows,
+                                                                 const float* __restrict__ grad,
+                                                                 ApplyArgs a, int64_t n_tiles) {
+  static_assert(HW == 32 || HW == 16 || HW == 8, "half-waves per block: 32, 16 or 8");
   constexpr int G = 32, D = 128, T = 32;
   __shared__ __attribute__((aligned(16))) float ps[G][2][D];
   __shared__ uint32_t fkey[G];
+  __shared__ uint32_t lrow[G];   // Tile32Edges::last_row of each walked tile
+  __shared__ uint8_t edge[G];    // bit 0: last_open, bit 1: first_cont
   __shared__ int skip;
   const int gi = threadIdx.x >> 5, gl = threadIdx.x & 31;
-  const int64_t t = (int64_t)blockIdx.x * G + gi;
-  const bool live = t < n_tiles;
+  const int64_t t0 = (int64_t)blockIdx.x * G;  // the group's first tile
   // Key-range walks only (the row-sharded dedup's owner halves: a.ranged, a kernel argument,
   // so the branch is uniform): a group with no key in [key_lo, n_rows) has nothing to sum or
   // write. The full-range walk (the production apply) skips the check (two dependent key loads
@@ -705,53 +716,82 @@ __global__ __launch_bounds__(1024) void seg_group32_kernel(const uint32_t* __res
     }
     __syncthreads();
     if (skip) {  // the walk would find no run in range: the same (empty) tile flags
-      if (gl == 0 && live) a.tile_flags[t] = 0;
+      if (gl == 0)
+        for (int j = gi; j < G && t0 + j < n_tiles; j += HW) a.tile_flags[t0 + j] = 0;
       return;
     }
   }
-  Tile32Edges e{};
-  if (live) e = tile32_walk<OPT, Q>(keys, pos, n, n_rows, grad, a, t, &ps[gi][0][0]);
-  if (gl == 0) fkey[gi] = live ? e.first_key : 0xFFFFFFFFu;
+  // One tile after another; the SGD queue is flushed inside tile32_walk, so no queued run passes
+  // from one tile to the next. Unrolled: kept as a loop, the walk's lane-dependent addresses are
+  // hoisted and held in VGPRs across it, and the SGD walk at its 128-VGPR limit then needs 24
+  // bytes of scratch per lane (HW = 16); unrolled it needs none. One round (HW = 32) is written
+  // without the loop: through a one-trip loop the lazy / Keras Adam walks need 28 bytes, not 16.
+  auto walk_tile = [&](const int j) {
+    const int64_t t = t0 + j;
+    if (t < n_tiles) {
+      const Tile32Edges e = tile32_walk<OPT, Q>(keys, pos, n, n_rows, grad, a, t, &ps[j][0][0]);
+      if (gl == 0) {
+        fkey[j] = e.first_key;
+        lrow[j] = e.last_row;
+        edge[j] = (uint8_t)((e.last_open ? 1 : 0) | (e.first_cont ? 2 : 0));
+      }
+    } else if (gl == 0) {
+      fkey[j] = 0xFFFFFFFFu;
+      edge[j] = 0;
+    }
+  };
+  if constexpr (HW == G) {
+    walk_tile(gi);
+  } else {
+#pragma unroll
+    for (int r = 0; r < G / HW; ++r) walk_tile(r * HW + gi);
+  }
   __syncthreads();
-  if (!live) return;
   const int col = gl * 4;
-  uint8_t gflag = 0;
-  if (e.last_open) {  // head of a spanning segment: its level-1 sum inside this group
-    const uint32_t row = e.last_row;
-    float acc[1][4];
-    {
-      const float4 h = *reinterpret_cast<const float4*>(&ps[gi][1][col]);
-      acc[0][0] = h.x; acc[0][1] = h.y; acc[0][2] = h.z; acc[0][3] = h.w;
+#pragma unroll 1
+  for (int r = 0; r < G / HW; ++r) {
+    const int j = r * HW + gi;
+    const int64_t t = t0 + j;
+    if (t >= n_tiles) return;  // tiles are live in order: none after this one either
+    const uint8_t ej = edge[j];
+    uint8_t gflag = 0;
+    if (ej & 1) {  // head of a spanning segment: its level-1 sum inside this group
+      const uint32_t row = lrow[j];
+      float acc[1][4];
+      {
+        const float4 h = *reinterpret_cast<const float4*>(&ps[j][1][col]);
+        acc[0][0] = h.x; acc[0][1] = h.y; acc[0][2] = h.z; acc[0][3] = h.w;
+      }
+      int u = j + 1;
+      for (; u < G && fkey[u] == row; ++u) {
+        const float4 c = *reinterpret_cast<const float4*>(&ps[u][0][col]);
+        acc[0][0] += c.x; acc[0][1] += c.y; acc[0][2] += c.z; acc[0][3] += c.w;
+      }
+      const int64_t tn = t0 + G;  // first tile of the next group
+      const bool crosses = u == G && tn < n_tiles && keys[tn * T] == row;
+      if (crosses) {
+        RowIO<4>::store(a.chunk + (t * 2 + 1) * (int64_t)D + col, acc[0]);
+        gflag = 1;
+      } else {
+        finalize_row<OPT, 4, 1>(a, row, gl, 32, acc,
+                                OPT == OPT_EMIT ? seg_id_of(a, keys, t * T + T - 1) : 0);
+      }
     }
-    int u = gi + 1;
-    for (; u < G && fkey[u] == row; ++u) {
-      const float4 c = *reinterpret_cast<const float4*>(&ps[u][0][col]);
-      acc[0][0] += c.x; acc[0][1] += c.y; acc[0][2] += c.z; acc[0][3] += c.w;
+    if (j == 0 && (ej & 2)) {  // the group's first tile continues a segment from before
+      const uint32_t fk = fkey[0];
+      float acc[4];
+      {
+        const float4 h = *reinterpret_cast<const float4*>(&ps[0][0][col]);
+        acc[0] = h.x; acc[1] = h.y; acc[2] = h.z; acc[3] = h.w;
+      }
+      for (int u = 1; u < G && fkey[u] == fk; ++u) {
+        const float4 c = *reinterpret_cast<const float4*>(&ps[u][0][col]);
+        acc[0] += c.x; acc[1] += c.y; acc[2] += c.z; acc[3] += c.w;
+      }
+      RowIO<4>::store(a.chunk + (t * 2) * (int64_t)D + col, acc);
     }
-    const int64_t tn = ((int64_t)blockIdx.x + 1) * G;  // first tile of the next group
-    const bool crosses = u == G && tn < n_tiles && keys[tn * T] == row;
-    if (crosses) {
-      RowIO<4>::store(a.chunk + (t * 2 + 1) * (int64_t)D + col, acc[0]);
-      gflag = 1;
-    } else {
-      finalize_row<OPT, 4, 1>(a, row, gl, 32, acc,
-                              OPT == OPT_EMIT ? seg_id_of(a, keys, t * T + T - 1) : 0);
-    }
+    if (gl == 0) a.tile_flags[t] = gflag;
   }
-  if (gi == 0 && e.first_cont) {  // the group's first tile continues a segment from before
-    const uint32_t fk = e.first_key;
-    float acc[4];
-    {
-      const float4 h = *reinterpret_cast<const float4*>(&ps[0][0][col]);
-      acc[0] = h.x; acc[1] = h.y; acc[2] = h.z; acc[3] = h.w;
-    }
-    for (int u = 1; u < G && fkey[u] == fk; ++u) {
-      const float4 c = *reinterpret_cast<const float4*>(&ps[u][0][col]);
-      acc[0] += c.x; acc[1] += c.y; acc[2] += c.z; acc[3] += c.w;
-    }
-    RowIO<4>::store(a.chunk + (t * 2) * (int64_t)D + col, acc);
-  }
-  if (gl == 0) a.tile_flags[t] = gflag;
 }
 
 // ---- fix-up of segments that span tiles ----------------------------------------------
@@ -1198,6 +1238,23 @@ __global__ __launch_bounds__(256) void keras_bitmap_mark_kernel(const uint32_t* 
 #ifndef RS_SGD_QUEUE
 #define RS_SGD_QUEUE 2
 #endif
+// Half-waves per block of the D = 128 group walk (seg_group32_kernel): 32, 16 or 8, that is
+// blocks of 1024 / 512 / 256 threads over the same aligned group of 32 tiles. Bit-identical at
+// every value; only the one given here is compiled. A/B builds: -DRS_APPLY_HW=32|16|8.
+// 16 is the step's choice, not the kernel's: alone the walk takes 213 us at 16 and 217 at 32,
+// but at 32 a block is a whole CU (16 waves x 128 VGPRs), every sort or dense-tail block that
+// lands on a CU shuts the walk out of it, and the walk takes 248 us in the step; at 16 it takes
+// 216 there. Interleaved A/B, 200 steps, 8 rounds: step 0.626-0.634 ms (parent), 0.622-0.636
+// (32), 0.612-0.621 (16), 0.653-0.662 (8: the queued SGD walk in four rounds needs 32 bytes of
+// scratch per lane). DESIGN.md section 6, profiles/apply_block_shape.txt.
+// The lazy / Keras Adam and element-wise Adagrad walks keep 32 whatever is given: in two rounds
+// they need 48 / 48 / 20 bytes of scratch per lane at 128 VGPRs against 16 / 16 / 0 in one.
+#ifndef RS_APPLY_HW
+#define RS_APPLY_HW 16
+#endif
+constexpr int apply_hw(int opt) {
+  return opt == OPT_LAZY || opt == OPT_KERAS || opt == OPT_ADAGRAD ? 32 : RS_APPLY_HW;
+}
 
 static int32_t launch_segments(int opt, const uint32_t* keys, const int32_t* pos, int64_t n,
                                int64_t n_rows, const float* grad, const ApplyArgs& a,
@@ -1232,12 +1289,13 @@ static int32_t launch_segments(int opt, const uint32_t* keys, const int32_t* pos
   RS_DISPATCH_VEC_CPL(geom, ({                                                                  \
     if (g32) {                                                                                  \
       if (OPTV == OPT_SGD)                                                                      \
-        seg_group32_kernel<OPTV, RS_SGD_QUEUE><<<ceil_div(n_tiles, 32), 1024, 0, st>>>(         \
-            keys, pos, n, (uint32_t)n_rows, grad, a, n_tiles);                                  \
+        seg_group32_kernel<OPTV, RS_SGD_QUEUE, apply_hw(OPTV)>                                  \
+            <<<ceil_div(n_tiles, 32), apply_hw(OPTV) * 32, 0, st>>>(                            \
+                keys, pos, n, (uint32_t)n_rows, grad, a, n_tiles);                              \
       else                                                                                      \
-        seg_group32_kernel<OPTV><<<ceil_div(n_tiles, 32), 1024, 0, st>>>(keys, pos, n,          \
-                                                                     (uint32_t)n_rows, grad, a, \
-                                                                     n_tiles);                  \
+        seg_group32_kernel<OPTV, 0, apply_hw(OPTV)>                                             \
+            <<<ceil_div(n_tiles, 32), apply_hw(OPTV) * 32, 0, st>>>(                            \
+                keys, pos, n, (uint32_t)n_rows, grad, a, n_tiles);                              \
     } else {                                                                                    \
       if (t32)                                                                                  \
         seg_tile32_kernel<OPTV><<<ceil_div(n_tiles, 8), 256, 0, st>>>(       \
