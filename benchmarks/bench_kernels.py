@@ -311,6 +311,82 @@ def topk_ip(iters, out, rounds=5):
     bench("eges_like", q, x, 10, None, 1)
 
 
+def din_activation(iters, out, rounds=5):
+    """DIN's LocalActivationUnit fused (csrc/din_activation.hip) against the unfused torch unit
+    with the same weights, at the cfg3 shape (B 4096, L 100, D 36), with synthetic_batch history
+    lengths (2 + Geometric(0.1)) and with full histories; forward alone and forward + backward,
+    interleaved in one process: `rounds` rounds of both paths, each timed with events over its
+    launches, medians reported with every round next to them. Roofline line: the `his` read
+    (forward) and the `his` reads + `dhis` write (forward + backward: his is read by both passes)
+    over the fused time. Also torch.cuda.max_memory_allocated around one forward + backward of
+    each path, above the memory held before it."""
+    from recommender_amd.dien.layers import LocalActivationUnit
+
+    B, T, D = 4096, 100, 36
+    units = []
+    for fused in (True, False):
+        g = torch.Generator(device=DEV).manual_seed(3)
+        units.append(LocalActivationUnit(D, device=DEV, generator=g, fused=fused))
+    gen = torch.Generator(device=DEV).manual_seed(4)
+    rng = np.random.default_rng(4)
+    tgt = (torch.randn(B, 1, D, device=DEV, generator=gen) * 0.5).requires_grad_(True)
+    his = (torch.randn(B, T, D, device=DEV, generator=gen) * 0.5).requires_grad_(True)
+    drep = torch.randn(B, D, device=DEV, generator=gen)
+    lens = np.clip(2 + rng.geometric(0.1, B), 2, T)
+    masks = {"synthetic": torch.from_numpy(np.arange(T)[None, :] < lens[:, None]).to(DEV),
+             "full": torch.ones(B, T, dtype=torch.bool, device=DEV)}
+    s = torch.cuda.current_stream()
+    for mname, mask in masks.items():
+        def fwd(u):
+            with torch.no_grad():
+                return u((tgt, his), mask=mask)
+
+        def fwd_bwd(u):
+            for p in (tgt, his, *u.parameters()):
+                p.grad = None
+            u((tgt, his), mask=mask).backward(drep)
+
+        peak = []
+        for u in units:
+            fwd_bwd(u)
+            for p in (tgt, his, *u.parameters()):
+                p.grad = None
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            fwd_bwd(u)
+            torch.cuda.synchronize()
+            peak.append(torch.cuda.max_memory_allocated() - base)
+        for what, fn, nbytes in (("fwd", fwd, B * T * D * 4), ("fwd+bwd", fwd_bwd, 3 * B * T * D * 4)):
+            times = {"fused": [], "unfused": []}
+            for u in units:
+                fn(u)
+            for _ in range(rounds):
+                for label, u in zip(("fused", "unfused"), units):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record(s)
+                    for _ in range(iters):
+                        fn(u)
+                    e1.record(s)
+                    torch.cuda.synchronize()
+                    times[label].append(e0.elapsed_time(e1) / iters * 1e3)
+            mf, mu = float(np.median(times["fused"])), float(np.median(times["unfused"]))
+            gbs = nbytes / (mf * 1e-6) / 1e9
+            line = {"kernel": f"din_activation {what}",
+                    "config": {"B": B, "L": T, "D": D, "mask": mname,
+                               "valid_steps": int(mask.sum())},
+                    "fused_us": round(mf, 1), "unfused_us": round(mu, 1),
+                    "speedup": round(mu / mf, 2), "his_dhis_bytes": int(nbytes),
+                    "fused_achieved_GBs": round(gbs, 1), "fused_frac_of_hbm_peak": round(gbs / PEAK, 4),
+                    "fwd_bwd_peak_alloc_MB": {"fused": round(peak[0] / 2 ** 20, 1),
+                                              "unfused": round(peak[1] / 2 ** 20, 1)},
+                    "fused_rounds_us": [round(t, 1) for t in times["fused"]],
+                    "unfused_rounds_us": [round(t, 1) for t in times["unfused"]]}
+            out.append(line)
+            print(json.dumps(line), flush=True)
+
+
 def embedding(iters, out):
     from recommender_amd.esmm import FEAT_VOCAB
     from recommender_amd.synthetic import aliccp_batch, scaled_vocab

@@ -8,7 +8,7 @@
   pinsage_infer: whole-catalogue PinSage inference at the ML-20M shape (get_item_reprs(32) against
               the layer-wise chain, unfused and fused) and the convolve alone on a 4M-item table
 Prints one JSON line per run with examples/sec and per-kernel HIP-event times.
-Usage: python benchmarks/bench_models.py --model dien|mmoe|esmm|deepfm|dlrm_cfg2|pinsage_infer [--steps K --warmup W]"""
+Usage: python benchmarks/bench_models.py --model dien|din [--din-fused 0|1]|mmoe|esmm|deepfm|dlrm_cfg2|pinsage_infer [--steps K --warmup W]"""
 from __future__ import annotations
 
 import argparse
@@ -46,8 +46,11 @@ def run(step_fn, batches, steps, warmup, watch):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="dien",
-                    choices=["dien", "mmoe", "esmm", "deepfm", "deepfm_file", "pinsage", "eges",
-                             "dlrm_cfg2", "pinsage_infer"])
+                    choices=["dien", "din", "mmoe", "esmm", "deepfm", "deepfm_file", "pinsage",
+                             "eges", "dlrm_cfg2", "pinsage_infer"])
+    ap.add_argument("--din-fused", type=int, default=0, choices=[0, 1],
+                    help="din: 1 = the local activation unit on the fused kernels "
+                         "(DIN(fused_activation=True)); 0 (default) = the torch path")
     ap.add_argument("--infer-items", type=int, default=4_000_000,
                     help="pinsage_infer: items of the synthetic table the convolve alone is timed on")
     ap.add_argument("--file-rows", type=int, default=1_000_000,
@@ -78,7 +81,7 @@ def main():
                     help="deepfm: graph = the Keras-Adam step captured once as a HIP graph and replayed "
                          "(TrainStep.capture_static); eager: TrainStep.__call__")
     ap.add_argument("--dien-mode", default="graph", choices=["eager", "graph"],
-                    help="dien: eager = DIENStep.__call__; graph = static_step captured once and "
+                    help="dien / din: eager = DIENStep.__call__; graph = static_step captured once and "
                          "replayed (DIENStep.capture)")
     ap.add_argument("--eges-mode", default="graph", choices=["eager", "graph"],
                     help="eges: eager = EGESStep.__call__ (SparseAdam keras); graph = static_step "
@@ -98,7 +101,7 @@ def main():
         return deepfm_from_file(args)
     if args.model == "pinsage_infer":
         return pinsage_infer_bench(args)
-    if args.tuned_gemms == 1 or (args.tuned_gemms < 0 and args.model in ("dien", "esmm", "mmoe")):
+    if args.tuned_gemms == 1 or (args.tuned_gemms < 0 and args.model in ("dien", "din", "esmm", "mmoe")):
         from recommender_amd.gemm_tuning import use_tuned_gemms
 
         use_tuned_gemms()
@@ -135,6 +138,37 @@ def main():
                  "rs_dien_attention_bwd", "rs_embedding_fwd", "rs_embedding_apply", "rs_keras_adam_dense_sweep"]
         cfg = {"workload": "dien_amazon_b4096_l100", "batch": B, "hist_len": 100, "gru_units": 36,
                "mode": args.dien_mode}
+    elif args.model == "din":
+        # the DIN train step at the cfg3 shape (B 4096, L 100), modelled on the dien branch
+        from recommender_amd.dien import DIN
+        from recommender_amd.dien.train import DIENStep, synthetic_batch
+
+        B = args.batch or 4096
+        m = DIN(fused_activation=bool(args.din_fused), item_vocab_size=63001, item_embedding_size=18,
+                cat_vocab_size=801, cat_embedding_size=18, mlp_units=[200, 80, 1], device=dev)
+        step = DIENStep(m)
+        batches = []
+        for _ in range(4):
+            f, lab = synthetic_batch(rng, B, 100, 63001, 801, negatives=False)
+            batches.append(({k: torch.from_numpy(v).to(dev) for k, v in f.items()}, torch.from_numpy(lab).to(dev)))
+        if args.dien_mode == "graph":
+            st_f = {k: torch.empty_like(v) for k, v in batches[0][0].items()}
+            st_l = torch.empty_like(batches[0][1])
+            dctr = {"n": 0, "replay": None}
+            train_d = step
+
+            def step(f, lab):
+                torch._foreach_copy_([st_f[k] for k in f] + [st_l], list(f.values()) + [lab])
+                dctr["n"] += 1
+                if dctr["n"] == 1:
+                    return train_d.static_step(st_f, st_l)
+                if dctr["replay"] is None:
+                    dctr["replay"] = train_d.capture(st_f, st_l)
+                return dctr["replay"]()
+        watch = ["rs_din_activation_fwd", "rs_din_activation_bwd", "rs_embedding_fwd",
+                 "rs_embedding_apply", "rs_keras_adam_dense_sweep"]
+        cfg = {"workload": "din_amazon_b4096_l100", "batch": B, "hist_len": 100,
+               "fused_activation": bool(args.din_fused), "mode": args.dien_mode}
     elif args.model in ("mmoe", "esmm"):
         from recommender_amd.esmm import FEAT_VOCAB
         from recommender_amd.esmm.train import MultiTaskStep, build
@@ -332,7 +366,7 @@ def main():
         del lz, m2
     out = {"model": args.model, "examples_per_sec": round(B / sec, 1),
            "ms_per_step": round(sec * 1e3, 3), "config": cfg, "kernels_us": k, **extra}
-    if args.cpu_baseline:
+    if args.cpu_baseline and args.model != "din":
         fns = {"deepfm": lambda: deepfm_cpu_baseline(B),
                "dlrm_cfg2": cfg2_cpu_baseline,
                "dien": dien_cpu_baseline,

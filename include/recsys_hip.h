@@ -658,6 +658,36 @@ int32_t rs_dien_aux_bwd_acc(const float* hidden, const float* pos, const float* 
                             int32_t acc_hidden, float* dpos, float* dneg, float* dparams,
                             void* workspace, size_t ws_bytes, void* stream);
 
+/* a-12 DIN LocalActivationUnit (dien/layers.py:34-59), fused forward and backward
+ *      (csrc/din_activation.hip). target [B,D], his [B,L,D], mask [B,L] u8; W1 [4D,80] in the
+ *      reference's row order ([t, h, t-h, t*h]), b1 [80], W2 [80,40], b2 [40], W3 [40], b3 [1].
+ *        w[b,t]  = σ(σ([t_b, h, t_b-h, t_b⊙h]·W1 + b1)·W2 + b2)·W3 + b3
+ *        rep[b]  = Σ_t m[b,t]·w[b,t]·his[b,t]                      (unnormalised, [B,D])
+ *      A step with m = 0 is SELECTED out, not multiplied by 0: it adds exactly 0 to every output
+ *      and its dhis row is exactly 0 whatever its history row holds. This differs from the
+ *      reference only where the reference gives NaN from a non-finite padding row. An
+ *      all-padding history gives rep[b] = 0 and dtarget[b] = 0 exactly (no 0/0 in this layer).
+ *      bwd: drep [B,D] → dtarget [B,D], dhis [B,L,D], dparams = [dW1 (4D×80) | db1 | dW2 | db2 |
+ *      dW3 | db3] (overwritten, deterministic). Every element of rep, dtarget, dhis and dparams
+ *      is written. The result of an example does not depend on the rest of the batch (rep,
+ *      dtarget, dhis bit for bit; dparams sums over the batch in a fixed order).
+ *      Built for D = 36 and D = 16 (RS_E_UNSUPPORTED otherwise); 1 <= L <= 4096; B = 0 returns
+ *      RS_OK (bwd zero-fills dparams). A workspace below rs_din_activation_workspace_size(B, L, D)
+ *      bytes is RS_E_WORKSPACE; null pointers and bad sizes RS_E_INVALID. No host
+ *      synchronisation and no allocation: graph-capturable.
+ *      Grids: both kernels are persistent over rounds of 4 examples (one wave each):
+ *        fwd blocks = min(ceil(B / 4), 3·CUs),  bwd blocks = min(ceil(B / 4), CUs). */
+size_t rs_din_activation_workspace_size(int64_t B, int32_t L, int32_t D);
+int32_t rs_din_activation_fwd(const float* target, const float* his, const uint8_t* mask,
+                              int64_t B, int32_t L, int32_t D, const float* W1, const float* b1,
+                              const float* W2, const float* b2, const float* W3, const float* b3,
+                              float* rep, void* workspace, size_t ws_bytes, void* stream);
+int32_t rs_din_activation_bwd(const float* target, const float* his, const uint8_t* mask,
+                              int64_t B, int32_t L, int32_t D, const float* W1, const float* b1,
+                              const float* W2, const float* b2, const float* W3, const float* b3,
+                              const float* drep, float* dtarget, float* dhis, float* dparams,
+                              void* workspace, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Keras binary_crossentropy on probabilities (ctr/train.py:85, dien/train.py:18,
  * esmm/train.py:101-102; [3p] TF 2.2 backend: clip to [eps, 1-eps], -(y log(p+eps) +

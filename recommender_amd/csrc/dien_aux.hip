@@ -24,7 +24,7 @@
 // partials are folded in a fixed order (fold_two_level).
 #include <algorithm>
 
-#include "common.hpp"
+#include "aux_mlp.hpp"  // the MFMA layer core, shared with din_activation.hip
 
 namespace rs {
 
@@ -36,14 +36,6 @@ size_t exclusive_scan_ws_size(int64_t n);
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int kN1 = 80, kN2 = 40;  // AuxiliaryNet([80, 40, 1])
-constexpr int kT1 = 5, kT2 = 3;    // 16-unit tiles of the two hidden layers (40 padded to 48)
-constexpr int kMaxIn = 80, kMaxKS = kMaxIn / 4;
-constexpr int kW1S = 81, kW2S = 49;  // LDS row strides: W1 [In][80], W2 [80][48] (bank spread)
-constexpr int kS1 = 81, kS2 = 49;    // wave scratch strides: [16 rows][80] and [16 rows][48]
-constexpr int kWaves = 4;
 constexpr int kBwdBlocksPerCU = 1;
 
 struct AuxArgs {
@@ -56,36 +48,11 @@ struct AuxArgs {
   const float *W1, *b1, *W2, *b2, *W3, *b3;  // [H+E, 80], [80], [80, 40], [40], [40], [1]
 };
 
-struct AuxLds {
-  float w1[kMaxIn * kW1S];
-  float w2[kN1 * kW2S];
-  float b1[kN1], b2[48], w3[48];
-};
-
-// σ with the hardware exp2 / reciprocal (≈1-2 ulp; the parity tests bound the net at 1e-5)
-__device__ __forceinline__ float aux_sigm(float x) {
-  return __builtin_amdgcn_rcpf(1.f + __expf(-x));
-}
-
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 __device__ void stage_weights(const AuxArgs& a, AuxLds& s) {
-  const int In = a.H + a.E;
-  for (int i = threadIdx.x; i < kMaxIn * kN1; i += blockDim.x) {
-    const int f = i / kN1, u = i % kN1;
-    s.w1[f * kW1S + u] = f < In ? a.W1[f * kN1 + u] : 0.f;
-  }
-  for (int i = threadIdx.x; i < kN1 * 48; i += blockDim.x) {
-    const int u = i / 48, v = i % 48;
-    s.w2[u * kW2S + v] = v < kN2 ? a.W2[u * kN2 + v] : 0.f;
-  }
+  stage_w1(s.w1, kMaxIn, a.H + a.E, a.W1);
+  stage_w2(s.w2, a.W2);
   for (int i = threadIdx.x; i < kN1; i += blockDim.x) s.b1[i] = a.b1[i];
-  for (int i = threadIdx.x; i < 48; i += blockDim.x) {
-    s.b2[i] = i < kN2 ? a.b2[i] : 0.f;
-    s.w3[i] = i < kN2 ? a.W3[i] : 0.f;
-  }
+  stage_b2_w3(s.b2, s.w3, a.b2, a.W3);
 }
 
 // Number of valid aux rows of example b: Σ_{t=1}^{L-1} mask[b, t] (wave-uniform).
@@ -132,41 +99,12 @@ template <int H, int E>
 __device__ __forceinline__ float aux_forward(const AuxArgs& a, const AuxLds& s,
                                              const float (&xv)[(H + E) / 4], int j, int kq,
                                              f4 (&h1)[kT1], f4 (&h2)[kT2]) {
-#pragma unroll
-  for (int u = 0; u < kT1; ++u) h1[u] = f4{0.f, 0.f, 0.f, 0.f};
-  const float* w1 = s.w1 + kq * kW1S + j;
-#pragma unroll
-  for (int k = 0; k < (H + E) / 4; ++k) {
-    const float* w = w1 + 4 * k * kW1S;  // A: W1[4k + kq][16u + j]
-#pragma unroll
-    for (int u = 0; u < kT1; ++u) h1[u] = mfma4(w[16 * u], xv[k], h1[u]);
-  }
+  mlp3_layer1<(H + E) / 4>(s.w1, xv, j, kq, h1);
 #pragma unroll
   for (int u = 0; u < kT1; ++u)
 #pragma unroll
     for (int r = 0; r < 4; ++r) h1[u][r] = aux_sigm(h1[u][r] + s.b1[16 * u + 4 * kq + r]);
-#pragma unroll
-  for (int m = 0; m < kT2; ++m) h2[m] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int u = 0; u < kT1; ++u)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float* w = s.w2 + (16 * u + 4 * kq + r) * kW2S + j;  // A: W2[16u+4kq+r][16m + j]
-#pragma unroll
-      for (int m = 0; m < kT2; ++m) h2[m] = mfma4(w[16 * m], h1[u][r], h2[m]);
-    }
-  float p = 0.f;
-#pragma unroll
-  for (int m = 0; m < kT2; ++m)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int v = 16 * m + 4 * kq + r;
-      h2[m][r] = aux_sigm(h2[m][r] + s.b2[v]);
-      p = fmaf(h2[m][r], s.w3[v], p);
-    }
-  p += __shfl_xor(p, 16);
-  p += __shfl_xor(p, 32);
-  return p + a.b3[0];
+  return mlp3_tail(s.w2, s.b2, s.w3, a.b3, j, kq, h1, h2);
 }
 
 // tf.nn.sigmoid_cross_entropy_with_logits(labels = y, logits = z)
@@ -287,16 +225,6 @@ struct BwdLds {
   float dxh[2][16 * kMaxH];  // the neg set's h-part input gradient, per item of the round
   int live[kSets];           // the set was computed this round
 };
-
-__device__ __forceinline__ void store4(float* p, f4 v) {  // 16-byte aligned global rows
-  *reinterpret_cast<f4*>(p) = v;
-}
-__device__ __forceinline__ void lds4(float* p, f4 v) {  // odd-stride LDS tile: 4 dword writes
-  p[0] = v[0];
-  p[1] = v[1];
-  p[2] = v[2];
-  p[3] = v[3];
-}
 
 template <int H, int E>
 __global__ __launch_bounds__(256) void aux_bwd_kernel(AuxArgs a, AuxGrad g) {
@@ -543,17 +471,6 @@ __global__ __launch_bounds__(256) void aux_bwd_kernel(AuxArgs a, AuxGrad g) {
 size_t bwd_lds_bytes() { return sizeof(BwdLds); }
 
 int bwd_blocks(int dev_cus) { return dev_cus * kBwdBlocksPerCU; }
-
-int device_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
 
 int32_t check_aux(const AuxArgs& a) {
   RS_CHECK_ARG(a.B >= 0 && a.L >= 2 && a.L <= 4096, "bad sizes (L >= 2)");

@@ -523,19 +523,101 @@ class MLP(nn.Module):
         return x
 
 
+DIN_FUSED_DIMS = (36, 16)  # the widths csrc/din_activation.hip is built for
+
+
+class _LocalActivationFn(torch.autograd.Function):
+    """LocalActivationUnit on the fused kernels (csrc/din_activation.hip): the net is evaluated
+    only on the 16-step tiles that hold a valid step, no [B·L, 4D] / [B·L, 80] / [B·L, 40] tensor
+    reaches HBM, and the backward recomputes the forward. Masked steps are selected out: their
+    dhis rows are exactly 0."""
+
+    @staticmethod
+    def forward(ctx, target, his, mask_u8, W1, b1, W2, b2, W3, b3):
+        B, T, D = his.shape
+        dev = his.device
+        rep = torch.empty(B, D, device=dev)
+        ws = _din_workspace(B, T, D, dev)
+        args = (target, his, mask_u8, B, T, D, W1, b1, W2, b2, W3, b3, rep, ws)
+        L.call("rs_din_activation_fwd", *[L.ptr(x) if isinstance(x, torch.Tensor) else x for x in args],
+               ws.numel(), L.stream_ptr(dev))
+        ctx.save_for_backward(target, his, mask_u8, W1, b1, W2, b2, W3, b3)
+        return rep
+
+    @staticmethod
+    def backward(ctx, drep):
+        target, his, mask_u8, W1, b1, W2, b2, W3, b3 = ctx.saved_tensors
+        B, T, D = his.shape
+        dev = his.device
+        dt = torch.empty_like(target)
+        dh = torch.empty_like(his)
+        n1, n2 = W1.shape[1], W2.shape[1]
+        dparams = torch.empty(4 * D * n1 + n1 + n1 * n2 + n2 + n2 + 1, device=dev)
+        ws = _din_workspace(B, T, D, dev)
+        args = (target, his, mask_u8, B, T, D, W1, b1, W2, b2, W3, b3, drep.contiguous(), dt, dh,
+                dparams, ws)
+        L.call("rs_din_activation_bwd", *[L.ptr(x) if isinstance(x, torch.Tensor) else x for x in args],
+               ws.numel(), L.stream_ptr(dev))
+        o = 0
+        outs = []
+        for shape in (W1.shape, b1.shape, W2.shape, b2.shape, W3.shape, b3.shape):
+            n = int(torch.Size(shape).numel())
+            outs.append(dparams[o:o + n].view(shape))
+            o += n
+        return (dt, dh, None, *outs)
+
+
+_din_ws: dict = {}
+
+
+def _din_workspace(B, T, D, dev):
+    nb = L.lib().rs_din_activation_workspace_size(B, T, D)
+    ws = _din_ws.get(dev)
+    if ws is None or ws.numel() < nb:
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        _din_ws[dev] = ws
+    return ws
+
+
 class LocalActivationUnit(nn.Module):
     """dien/layers.py:34-59 (DIN): unnormalised weights Dense(80σ)→Dense(40σ)→Dense(1) on
-    [t, h, t-h, t·h], masked, then weightsᵀ·H."""
+    [t, h, t-h, t·h], masked, then weightsᵀ·H. fused=True runs GPU inputs on the kernels of
+    csrc/din_activation.hip (_LocalActivationFn; dim 36 or 16); inputs that are not on the GPU
+    keep the torch path."""
 
-    def __init__(self, dim, device=None, generator=None):
+    def __init__(self, dim, device=None, generator=None, fused=False):
         super().__init__()
+        if fused and dim not in DIN_FUSED_DIMS:
+            raise ValueError(f"fused LocalActivationUnit is built for dim in {DIN_FUSED_DIMS}, "
+                             f"got {dim}")
+        self.dim, self.fused = dim, bool(fused)
         self.layer_1 = Dense(80, "sigmoid", in_features=4 * dim, device=device, generator=generator)
         self.layer_2 = Dense(40, "sigmoid", in_features=80, device=device, generator=generator)
         self.layer_3 = Dense(1, None, in_features=40, device=device, generator=generator)
 
+    def _fused_ready(self, target, history):
+        """GPU inputs run on the kernels (a shape they do not take is an error, not a reason to
+        fall back); inputs that are not on the GPU take the torch path, so CPU-built models work."""
+        if not (self.fused and history.is_cuda and target.is_cuda):
+            return False
+        if (history.dtype != torch.float32 or target.dtype != torch.float32
+                or history.shape[-1] != self.dim or history.shape[1] < 1
+                or target.numel() != history.shape[0] * self.dim):
+            raise ValueError(f"fused LocalActivationUnit({self.dim}): fp32 target [B, 1, {self.dim}] "
+                             f"and history [B, L >= 1, {self.dim}] expected, got "
+                             f"{tuple(target.shape)} {target.dtype}, {tuple(history.shape)} "
+                             f"{history.dtype}")
+        return True
+
     def forward(self, inputs, mask=None):
         target, history = inputs
         B, T, D = history.shape
+        if self._fused_ready(target, history):
+            l1, l2, l3 = self.layer_1, self.layer_2, self.layer_3
+            m = _mask_u8(mask, history.shape[:2], history.device)
+            return _LocalActivationFn.apply(target.reshape(B, D).contiguous(), history.contiguous(),
+                                            m, l1.kernel, l1.bias, l2.kernel, l2.bias, l3.kernel,
+                                            l3.bias)
         t = target.expand(B, T, D)
         c = torch.cat([t, history, t - history, t * history], -1).reshape(B * T, 4 * D)
         w = self.layer_3(self.layer_2(self.layer_1(c))).view(B, T, 1)

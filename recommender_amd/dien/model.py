@@ -77,15 +77,24 @@ class BaseModel(nn.Module):
 
 
 class DIN(BaseModel):
-    def __init__(self, **kwargs):
+    def __init__(self, fused_activation=False, **kwargs):
+        """fused_activation: the local activation unit on the fused kernels
+        (LocalActivationUnit(fused=True), embedding width 36 or 16). Masked history steps then
+        receive gradient rows of exactly 0, so the history lookups leave them out (grad_mask)."""
         super().__init__(**kwargs)
+        self.fused_activation = bool(fused_activation)
         self.local_activation_unit = LocalActivationUnit(self.embedding_dim, kwargs.get("device"),
-                                                         kwargs.get("generator"))
+                                                         kwargs.get("generator"),
+                                                         fused=self.fused_activation)
 
     def forward(self, inputs, training=False, mask=None):
         mask = self.item_embedding.compute_mask(inputs["pos_his_item"])
         target = self.compute_flat_embedding((inputs["target_item"], inputs["target_cat"]))
-        his = self.compute_flat_embedding((inputs["pos_his_item"], inputs["pos_his_cat"]))
+        grad_mask = None
+        if self.fused_activation:
+            # masked steps are selected out: their gradient rows are exactly 0 (as DIEN.forward)
+            mask = grad_mask = mask.to(torch.uint8)
+        his = self.compute_flat_embedding((inputs["pos_his_item"], inputs["pos_his_cat"]), grad_mask)
         rep = self.local_activation_unit((target, his), mask=mask)
         return self.mlp(torch.cat([target.squeeze(1), rep], -1), training=training)
 

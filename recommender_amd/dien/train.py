@@ -114,6 +114,9 @@ def main(argv=None):
     ap.add_argument("--hip_graph", type=int, default=1,
                     help="1: the step captured once as a HIP graph (DIENStep.capture) and replayed "
                          "on each batch; 0: the eager step")
+    ap.add_argument("--fused_din", type=int, default=0,
+                    help="1: DIN's local activation unit on the fused kernels "
+                         "(DIN(fused_activation=True)); 0: the torch path")
     args = ap.parse_args(argv)
     from ..gemm_tuning import use_tuned_gemms
 
@@ -124,7 +127,7 @@ def main(argv=None):
     if args.model_type == "DIEN":
         model = DIEN(36, 36, **kw)
     elif args.model_type == "DIN":
-        model = DIN(**kw)
+        model = DIN(fused_activation=bool(args.fused_din), **kw)
     else:
         model = BaseModel(**kw)
     step = DIENStep(model)
