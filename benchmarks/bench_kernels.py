@@ -533,6 +533,79 @@ def embedding_bag(iters, out, rounds=5):
         torch.cuda.empty_cache()
 
 
+def embedding_q8(iters, out, rounds=5):
+    """Row-wise int8 tables against the fp32 ones, interleaved in one process (`rounds` rounds of
+    every variant, each timed over `iters` launches; medians reported, every round's time next to
+    them). One table of 8M rows, D = 128 and 64 (fp32 4 / 2 GB, q8 1.15 GB / 640 MB: all well past
+    the 256 MB Infinity Cache), 2M int32 ids, uniform and the bench's Zipf(1.05) spread over the
+    table; both sides read the same ids. Lookup: rs_embedding_q8_fwd against rs_embedding_fwd.
+    Bag (mean, fixed length 1, 10, 100): rs_embedding_bag_q8_fwd against rs_embedding_bag_fwd.
+    Bytes: every id 4, every row read once (4 D fp32, q_ld quantised), every output row 4 D."""
+    from recommender_amd.synthetic import _spread, bounded_zipf
+
+    rng = np.random.default_rng(4)
+    st = L.stream_ptr(torch.device(DEV))
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    V, n = 8_000_000, 2_097_152
+    id_sets = {"uniform": rng.integers(0, V, n).astype(np.int32),
+               "zipf1.05": _spread(bounded_zipf(rng, n, V), V).astype(np.int32)}
+    for D in (128, 64):
+        table = torch.empty(V, D, device=DEV).uniform_(-0.05, 0.05)
+        q_ld = int(L.lib().rs_q8_row_bytes(D))
+        qt = torch.empty(V, q_ld, dtype=torch.uint8, device=DEV)
+
+        def quant():
+            L.call("rs_quantize_rows_q8", L.ptr(table), D, V, D, L.ptr(qt), q_ld, L.ptr(err), st)
+
+        report("rs_quantize_rows_q8", {"rows": V, "D": D, "q_ld": q_ld}, timed(quant, 3),
+               V * (4 * D + q_ld), out)
+        outp = torch.empty(n, D, device=DEV)
+        for dist, ids_np in id_sets.items():
+            ids = torch.from_numpy(ids_np).to(DEV)
+
+            def lookup_f():
+                L.call("rs_embedding_fwd", L.ptr(table), V, D, L.ptr(ids), 0, n, None, 1,
+                       L.ptr(outp), L.ptr(err), st)
+
+            def lookup_q():
+                L.call("rs_embedding_q8_fwd", L.ptr(qt), V, D, q_ld, L.ptr(ids), 0, n, None, 1,
+                       L.ptr(outp), D, L.ptr(err), st)
+
+            def bag_f(nb, bl):
+                L.call("rs_embedding_bag_fwd", L.ptr(table), V, D, L.ptr(ids), 0, nb * bl, None,
+                       nb, bl, None, None, L.RS_BAG_MEAN, None, 1, L.ptr(outp), D, None,
+                       L.ptr(err), st)
+
+            def bag_q(nb, bl):
+                L.call("rs_embedding_bag_q8_fwd", L.ptr(qt), q_ld, V, D, L.ptr(ids), 0, nb * bl,
+                       None, nb, bl, None, None, L.RS_BAG_MEAN, None, 1, L.ptr(outp), D, None,
+                       L.ptr(err), st)
+
+            variants = [("lookup", "fp32", lookup_f, n * (8 * D + 4)),
+                        ("lookup", "q8", lookup_q, n * (q_ld + 4 * D + 4))]
+            for bl in (1, 10, 100):
+                nb = n // bl
+                variants.append((f"bag L={bl}", "fp32", lambda nb=nb, bl=bl: bag_f(nb, bl),
+                                 nb * bl * (4 * D + 4) + nb * 4 * D))
+                variants.append((f"bag L={bl}", "q8", lambda nb=nb, bl=bl: bag_q(nb, bl),
+                                 nb * bl * (q_ld + 4) + nb * 4 * D))
+            times = {v[:2]: [] for v in variants}
+            for _ in range(rounds):
+                for what, side, fn, _ in variants:
+                    times[(what, side)].append(timed(fn, iters))
+            med = {k: float(np.median(v)) for k, v in times.items()}
+            for what, side, _, nbytes in variants:
+                cfg = {"rows": V, "D": D, "q_ld": q_ld, "n_ids": n, "ids": dist,
+                       "rounds_us": [round(t, 1) for t in times[(what, side)]]}
+                if side == "q8":
+                    cfg["fp32_over_q8_time"] = round(med[(what, "fp32")] / med[(what, "q8")], 3)
+                report(f"embedding_q8 {what}: {side} (interleaved, median of {rounds})", cfg,
+                       med[(what, side)], nbytes, out)
+        assert int(err.item()) == 0
+        del table, qt, outp
+        torch.cuda.empty_cache()
+
+
 def criteo(iters, out):
     """Criteo TSV ingestion: line index + parse + vocab lookup over a ~45 MB synthetic text
     (algorithmic bytes: text read once, outputs written once)."""

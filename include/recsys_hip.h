@@ -44,6 +44,7 @@ extern "C" {
 #define RS_ERRBIT_FORMAT 2  /* a malformed input record (rs_tfrecord_parse_criteo) */
 #define RS_ERRBIT_RANGE 4   /* a size past what the caller declared (rs_sort_ids_slots: a slot
                                with more rows than max_slot_rows allows; the output is not sorted) */
+#define RS_ERRBIT_NONFINITE 8 /* a row that cannot be quantised (rs_quantize_rows_q8) */
 
 /* optimizer kinds for rs_embedding_apply */
 #define RS_OPT_SGD 0        /* var[u] -= lr * g_u                         (ctr/train.py:77-79) */
@@ -171,6 +172,62 @@ int32_t rs_embedding_bag_expand_grad(const float* dout, int64_t dout_ld, int32_t
                                      int32_t bag_len, const float* bag_scale,
                                      const float* per_sample_weights, float* grad_rows,
                                      void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * a-1c  Row-wise int8 tables for serving (RS_Q8; FBGEMM's "fused 8-bit row-wise" idea, the
+ * header first): quantise a trained fp32 table, read it back, gather rows, pool bags. Forward
+ * only; no reference counterpart (the reference serves its fp32 Keras tables).
+ *
+ * Row format. A quantised table is uint8 [n_rows, q_ld]; row r starts at byte r * q_ld and holds
+ *   bytes [0, 4) scale (float32), [4, 8) bias (float32), [8, 8 + dim) one uint8 code per column,
+ *   [8 + dim, q_ld) zero padding. rs_q8_row_bytes(dim) = round_up(8 + dim, 16) is the default
+ *   q_ld (0 for dim <= 0). Every entry point takes q_ld: q_ld >= 8 + dim, q_ld % 4 == 0, and the
+ *   table 4-byte aligned. Alignment chooses the access width, never the bits (rs_topk_ip's
+ *   rule): quantise writes 16-byte pieces when the table is 16-byte aligned and q_ld % 16 == 0,
+ *   the bag reads 8-byte pieces when both are multiples of 8, and 4-byte accesses serve the rest
+ *   (the lookup always: its stores, not its loads, set its speed).
+ * Quantise (fixed: results are bit-reproducible), per row over its dim columns:
+ *   lo = min + 0.f, hi = max + 0.f (exact in any order; the + 0.f turns -0 into +0),
+ *   bias = lo, scale = (hi - lo) / 255.f (IEEE subtraction and division);
+ *   scale == 0.f (a constant row, or a range whose quotient rounds to 0): every code is 0;
+ *   otherwise code = (uint8) min(max(rintf((x - lo) / scale), 0.f), 255.f), ties to even, IEEE
+ *   subtraction and division (the clamp matters: with a subnormal scale the quotient passes 255).
+ *   A row with a NaN or +-inf element, or whose hi - lo overflows, is written as scale 0, bias 0,
+ *   all codes 0 and sets RS_ERRBIT_NONFINITE in err_flag (may be NULL). The padding bytes are
+ *   written as 0: a quantised table is a function of its input alone.
+ * Dequantise: v = __fadd_rn(__fmul_rn((float)code, scale), bias) — never an fma.
+ *
+ * rs_quantize_rows_q8: source row r at table + r * ld (floats), ld >= dim.
+ * rs_dequantize_rows_q8: out row r at out + r * out_ld (floats), out_ld >= dim; only the dim
+ *   columns are written.
+ * rs_embedding_q8_fwd: rs_embedding_fwd_strided over the dequantised rows (slab slots, i32 / i64
+ *   ids; an out-of-range id, negatives included, writes a zero row and sets RS_ERRBIT_OOB; only
+ *   the dim columns of a row are written). n_rows must be > 0 when n_ids > 0: row 0 is what an
+ *   out-of-range id reads and discards.
+ * rs_embedding_bag_q8_fwd: rs_embedding_bag_fwd's arguments with (qtable, q_ld) in place of
+ *   table, and its contract with "the table element" read as the dequantised element: ascending
+ *   position order, __fadd_rn, __fmul_rn(w[p], t) with weights, the mean an IEEE division, an
+ *   empty bag +0, bag_scale, malformed offsets, masks, slots. So the result equals, bit for bit,
+ *   rs_embedding_bag_fwd over the table rs_dequantize_rows_q8 writes.
+ * Errors: RS_E_INVALID for null pointers, dim <= 0, q_ld < 8 + dim, q_ld % 4 != 0, a table not
+ *   4-byte aligned, ld or out_ld below dim, and rs_embedding_bag_fwd's argument errors.
+ *   n_rows == 0 (quantise, dequantise), n_ids == 0 and n_bags == 0 are no-ops. */
+size_t rs_q8_row_bytes(int32_t dim);
+int32_t rs_quantize_rows_q8(const float* table, int64_t ld, int64_t n_rows, int32_t dim,
+                            uint8_t* qtable, int64_t q_ld, int32_t* err_flag, void* stream);
+int32_t rs_dequantize_rows_q8(const uint8_t* qtable, int64_t n_rows, int32_t dim, int64_t q_ld,
+                              float* out, int64_t out_ld, void* stream);
+int32_t rs_embedding_q8_fwd(const uint8_t* qtable, int64_t n_rows, int32_t dim, int64_t q_ld,
+                            const void* ids, int32_t id_dtype, int64_t n_ids,
+                            const int64_t* slot_offsets, int32_t n_slots, float* out,
+                            int64_t out_ld, int32_t* err_flag, void* stream);
+int32_t rs_embedding_bag_q8_fwd(const uint8_t* qtable, int64_t q_ld, int64_t n_rows, int32_t dim,
+                                const void* ids, int32_t id_dtype, int64_t n_ids,
+                                const int64_t* offsets, int64_t n_bags, int32_t bag_len,
+                                const uint8_t* valid, const float* per_sample_weights,
+                                int32_t mode, const int64_t* slot_offsets, int32_t n_slots,
+                                float* out, int64_t out_ld, float* bag_scale, int32_t* err_flag,
+                                void* stream);
 
 /* ------------------------------------------------------------------------------------
  * a-2 (part 1) Duplicate-index coalescing: the IndexedSlices gradient's `unique` +

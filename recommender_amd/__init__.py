@@ -8,6 +8,7 @@ from . import _lib  # noqa: F401
 __version__ = "0.1.0"
 
 _TABLES = ("Embedding", "EmbeddingBag", "SlabEmbedding")
+_QUANTIZED = ("QuantizedEmbedding", "QuantizedEmbeddingBag", "from_float", "quantize_embeddings")
 
 
 def __getattr__(name):
@@ -15,4 +16,7 @@ def __getattr__(name):
     if name in _TABLES:
         from . import embedding
         return getattr(embedding, name)
+    if name in _QUANTIZED:
+        from . import quantized
+        return getattr(quantized, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

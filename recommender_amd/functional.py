@@ -797,3 +797,103 @@ def topk_inner_product(queries, items, k: int, exclude=None, exclude_base: int =
            L.ptr(ip), L.ptr(it), L.ptr(one), k, n_splits, L.ptr(idx), L.ptr(val), L.ptr(ws),
            ws.numel() if ws is not None else 0, L.stream_ptr(dev))
     return idx, val
+
+
+# ---- row-wise int8 tables (include/recsys_hip.h a-1c): forward only, no autograd -----------
+def q8_row_bytes(dim: int) -> int:
+    """The default row stride of a quantised table of `dim` columns (rs_q8_row_bytes)."""
+    return int(L.lib().rs_q8_row_bytes(int(dim)))
+
+
+def quantize_rows(weight: torch.Tensor, q_ld: int | None = None,
+                  err_flag: torch.Tensor | None = None) -> torch.Tensor:
+    """The RS_Q8 table (uint8 [n_rows, q_ld]) of an fp32 [n_rows, dim] device tensor, read where
+    it lies when its rows are row-strided (rs_quantize_rows_q8). err_flag (device int32 [1])
+    gets RS_ERRBIT_NONFINITE when a row cannot be quantised; that row is written as zeros."""
+    w, ld = _row_major(weight, "weight")
+    n_rows, dim = w.shape
+    q_ld = q8_row_bytes(dim) if q_ld is None else int(q_ld)
+    q = torch.empty(n_rows, max(q_ld, 0), dtype=torch.uint8, device=w.device)
+    L.call("rs_quantize_rows_q8", L.ptr(w), ld, n_rows, dim, L.ptr(q), q_ld, L.ptr(err_flag),
+           L.stream_ptr(w.device))
+    return q
+
+
+def dequantize_rows(qweight: torch.Tensor, dim: int) -> torch.Tensor:
+    """The fp32 [n_rows, dim] table a contiguous RS_Q8 table stands for (rs_dequantize_rows_q8)."""
+    L.require_device(qweight, "qweight")
+    n_rows, q_ld = qweight.shape
+    out = torch.empty(n_rows, dim, device=qweight.device, dtype=torch.float32)
+    L.call("rs_dequantize_rows_q8", L.ptr(qweight), n_rows, dim, q_ld, L.ptr(out), dim,
+           L.stream_ptr(qweight.device))
+    return out
+
+
+def embedding_lookup_q8(table_module, ids: torch.Tensor) -> torch.Tensor:
+    """embedding_lookup over a quantised table (QuantizedEmbedding: qweight, output_dim,
+    slot_offsets, err_flag): [*ids.shape, dim] dequantised rows (rs_embedding_q8_fwd)."""
+    q = table_module.qweight
+    L.require_device(q, "quantised table")
+    ids = _ids_flat(ids)
+    dim = table_module.output_dim
+    out = torch.empty(*ids.shape, dim, device=q.device, dtype=torch.float32)
+    so = table_module.slot_offsets
+    n_slots = 1 if so is None else so.numel() - 1
+    L.call("rs_embedding_q8_fwd", L.ptr(q), q.shape[0], dim, q.shape[1], L.ptr(ids),
+           L.id_dtype_code(ids), ids.numel(), L.ptr(so), n_slots, L.ptr(out), dim,
+           L.ptr(table_module.err_flag), L.stream_ptr(q.device))
+    return out
+
+
+def embedding_bag_q8(table_module, ids: torch.Tensor, offsets: torch.Tensor | None = None, *,
+                     mode: str = "mean", valid: torch.Tensor | None = None,
+                     per_sample_weights: torch.Tensor | None = None,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """embedding_bag over a quantised table (rs_embedding_bag_q8_fwd): the same arguments and the
+    same result, bit for bit, as embedding_bag over the dequantised table."""
+    if mode not in BAG_MODES:
+        raise ValueError("embedding_bag_q8: mode must be 'sum' or 'mean'")
+    if per_sample_weights is not None and mode != "sum":
+        raise ValueError("embedding_bag_q8: per_sample_weights go with mode='sum' only")
+    q = table_module.qweight
+    L.require_device(q, "quantised table")
+    ids = _ids_flat(ids)
+    dim = table_module.output_dim
+    n = ids.numel()
+    if offsets is None:
+        if ids.dim() < 2:
+            raise ValueError("embedding_bag_q8: ids [n_bags, L] when no offsets are given")
+        bag_len = ids.shape[-1]
+        n_bags = torch.Size(ids.shape[:-1]).numel()
+    else:
+        L.require_device(offsets, "offsets")
+        if ids.dim() != 1 or offsets.dim() != 1 or offsets.dtype != torch.int64 \
+                or offsets.numel() < 1:
+            raise ValueError("embedding_bag_q8: ids [n_ids] with offsets int64 [n_bags + 1]")
+        offsets = offsets.contiguous()
+        bag_len, n_bags = 0, offsets.numel() - 1
+    if valid is not None:
+        L.require_device(valid, "valid")
+        if valid.numel() != n:
+            raise ValueError("embedding_bag_q8: valid holds one flag per id")
+        valid = valid.reshape(-1).to(torch.uint8).contiguous()
+    if per_sample_weights is not None:
+        L.require_device(per_sample_weights, "per_sample_weights")
+        if per_sample_weights.numel() != n:
+            raise ValueError("embedding_bag_q8: per_sample_weights holds one weight per id")
+        per_sample_weights = per_sample_weights.detach().reshape(-1).float().contiguous()
+    if out is None:
+        out = torch.empty(n_bags, dim, device=q.device, dtype=torch.float32)
+    else:
+        L.require_device(out, "out")
+        if (tuple(out.shape) != (n_bags, dim) or out.dtype != torch.float32
+                or (n_bags > 0 and out.stride(1) != 1) or (n_bags > 1 and out.stride(0) < dim)):
+            raise ValueError(f"embedding_bag_q8: out must be float32 [{n_bags}, {dim}] rows")
+    so = table_module.slot_offsets
+    n_slots = 1 if so is None else so.numel() - 1
+    L.call("rs_embedding_bag_q8_fwd", L.ptr(q), q.shape[1], q.shape[0], dim, L.ptr(ids),
+           L.id_dtype_code(ids), n, L.ptr(offsets), n_bags, bag_len, L.ptr(valid),
+           L.ptr(per_sample_weights), BAG_MODES[mode], L.ptr(so), n_slots, L.ptr(out),
+           out.stride(0) if n_bags > 1 else dim, None, L.ptr(table_module.err_flag),
+           L.stream_ptr(q.device))
+    return out
