@@ -831,7 +831,9 @@ int32_t rs_index_add_rows(const void* ids, int32_t id_dtype, int64_t n, const ui
  * ids >= n_rows read a zero row and set RS_ERRBIT_OOB in err_flag, which may be NULL).
  * Backward: dh [n_rows, D] contiguous = the loss's gradient (dloss: device float [1]); every
  * pair's four row terms are written as rows and folded per node by rs_index_add_rows (fixed
- * order: deterministic, no float atomics). D <= 64. */
+ * order: deterministic, no float atomics). Without a live pair (n_live 0) the loss is 0 / 0 = NaN
+ * and the nodes of every pair whose hinge is active take NaN, as the masked mean's backward gives.
+ * D <= 64. */
 size_t rs_pair_margin_workspace_size(int64_t n_pairs);
 int32_t rs_pair_margin_fwd(const float* h, int64_t ld, int32_t D, int64_t n_rows,
                            const int32_t* pos_src, const int32_t* pos_dst, const int32_t* neg_src,

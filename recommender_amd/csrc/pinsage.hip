@@ -614,8 +614,13 @@ __global__ __launch_bounds__(kPairThreads) void pair_margin_terms_kernel(
   bool oob = false;
   const int a = pair_row(ps[i], n_rows, oob), b = pair_row(pd[i], n_rows, oob);
   const int c = pair_row(ns[i], n_rows, oob), e = pair_row(nd[i], n_rows, oob);
-  const bool on = (valid == nullptr || valid[i]) && ((neg[i] + delta) - pos[i] >= 0.f);
-  const float g = on ? dloss[0] / (float)(n_live ? n_live[0] : P) : 0.f;
+  // the hinge's gradient as the mask-and-mean it replaces forms it: (dloss / n_live) · valid. A
+  // masked pair gets 0 — unless no pair is live (n_live 0: the loss is 0 / 0), where that product
+  // is inf · 0 = NaN and every active hinge hands it on, as margin_loss's backward does
+  const float q = dloss[0] / (float)(n_live ? n_live[0] : P);
+  const bool unmasked = valid == nullptr || valid[i];
+  const bool on = (unmasked || !isfinite(q)) && ((neg[i] + delta) - pos[i] >= 0.f);
+  const float g = on ? (unmasked ? q : NAN) : 0.f;
   const float ha = a >= 0 ? h[(int64_t)a * ld + d] : 0.f, hb = b >= 0 ? h[(int64_t)b * ld + d] : 0.f;
   const float hc = c >= 0 ? h[(int64_t)c * ld + d] : 0.f, he = e >= 0 ? h[(int64_t)e * ld + d] : 0.f;
   terms[(0 * P + i) * D + d] = -g * hb;

@@ -822,7 +822,8 @@ def test_pair_margin_loss_fused_matches_scorer_and_margin(padded):
     live-pair mean and its gradient in one kernel each way) against item2item_scorer +
     margin_loss by autograd: loss and dL/dh within fp32 rounding; shared nodes across pairs (the
     backward scatter collides), padding pairs (-1 ids, valid 0) scoring node 0 with no weight,
-    a hinge exactly at 0."""
+    a pair whose negative is its positive (hinge exactly delta; the hinge exactly at 0 is
+    tests/test_pinsage_edges_gpu.py's)."""
     from recommender_amd.pinsage.graph import PairGraph
     from recommender_amd.pinsage.model import item2item_scorer, margin_loss, pair_margin_loss
 
