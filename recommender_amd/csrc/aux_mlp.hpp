@@ -13,8 +13,6 @@
 namespace rs {
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 constexpr int kN1 = 80, kN2 = 40;  // AuxiliaryNet([80, 40, 1])
 constexpr int kT1 = 5, kT2 = 3;    // 16-unit tiles of the two hidden layers (40 padded to 48)
 constexpr int kMaxIn = 80, kMaxKS = kMaxIn / 4;
@@ -115,17 +113,6 @@ __device__ __forceinline__ void lds4(float* p, f4 v) {  // odd-stride LDS tile: 
   p[1] = v[1];
   p[2] = v[2];
   p[3] = v[3];
-}
-
-inline int device_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
 }
 
 }  // namespace

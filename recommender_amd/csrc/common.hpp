@@ -54,8 +54,44 @@ struct Carver {
   bool ok() const { return off <= cap; }
 };
 
+// compute units of the current device (256 if it cannot be asked), read once per process
+inline int device_cus() {
+  static const int n = [] {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus <= 0) {
+      (void)hipGetLastError();
+      return 256;
+    }
+    return cus;
+  }();
+  return n;
+}
+
+// ---- device-wide primitives other kernel files call (sort.hip unless noted) ---------
+int32_t radix_sort_pairs(uint32_t* keys_in, int32_t* vals_in, uint32_t* keys_out,
+                         int32_t* vals_out, int64_t n, int64_t n_rows, void* ws, size_t ws_bytes,
+                         hipStream_t st);
+size_t radix_sort_ws_size(int64_t n);
+int32_t exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, int32_t* total, void* ws,
+                           size_t ws_bytes, hipStream_t st);
+size_t exclusive_scan_ws_size(int64_t n);
+// fixed two-level fold of nchunks partial rows [N] into out[N] (dense.hip); part2 holds
+// 32 x N floats of scratch
+int32_t fold_two_level(const float* part, int nchunks, int N, float* part2, float* out,
+                       hipStream_t st);
+
 // ---- device helpers ------------------------------------------------------------------
 constexpr int kWave = 64;
+
+// register vectors (clang ext_vector_type: element-wise arithmetic, MFMA operands and results)
+typedef float f2 __attribute__((ext_vector_type(2)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ int64_t load_id(const void* ids, int32_t dtype, int64_t i) {
   return dtype == RS_ID_I64 ? static_cast<const int64_t*>(ids)[i]
@@ -80,6 +116,26 @@ __device__ __forceinline__ int64_t global_row(const void* ids, int32_t dtype, in
 
 __device__ __forceinline__ void flag_oob(int32_t* err_flag) {
   if (err_flag) atomicOr(err_flag, RS_ERRBIT_OOB);
+}
+// one OR per wave if any of its lanes saw an out-of-table id
+__device__ __forceinline__ void flag_oob_wave(bool oob, int32_t* err_flag) {
+  if (__any(oob) && (threadIdx.x & 63) == 0) flag_oob(err_flag);
+}
+
+// full-wave xor butterflies: every lane ends with the result, summed in one fixed order
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+// lane k's value (k wave-uniform), as a scalar operand
+__device__ __forceinline__ float read_lane(float v, int k) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
 }
 
 }  // namespace rs

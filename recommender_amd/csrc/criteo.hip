@@ -18,10 +18,6 @@
 
 namespace rs {
 
-int32_t exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, int32_t* total, void* ws,
-                           size_t ws_bytes, hipStream_t st);
-size_t exclusive_scan_ws_size(int64_t n);
-
 constexpr int kLineBlock = 4096;  // bytes per newline-count block
 
 // the imputation token of an empty categorical field in column c (deterministic stand-in for
@@ -213,12 +209,19 @@ inline unsigned grid256(int64_t n) { return (unsigned)ceil_div(n < 1 ? 1 : n, 25
 
 using namespace rs;
 
+// workspace of rs_line_index and rs_vocab_collect: n counts or flags, their n scanned offsets
+// and the scan's own scratch (a braced list: the takes run in the order written)
+struct ScanWs {
+  int32_t *in, *offs;
+  void* sws;
+};
+static ScanWs scan_ws(Carver& c, int64_t n) {
+  return {c.take<int32_t>(n), c.take<int32_t>(n), c.take<char>(exclusive_scan_ws_size(n))};
+}
+
 extern "C" size_t rs_line_index_workspace_size(int64_t n_bytes) {
-  const int64_t nb = ceil_div(n_bytes < 1 ? 1 : n_bytes, kLineBlock);
   Carver c(nullptr, 0);
-  c.take<int32_t>(nb);
-  c.take<int32_t>(nb);
-  c.take<char>(exclusive_scan_ws_size(nb));
+  scan_ws(c, ceil_div(n_bytes < 1 ? 1 : n_bytes, kLineBlock));
   return c.off + 256;
 }
 
@@ -229,9 +232,7 @@ extern "C" int32_t rs_line_index(const uint8_t* text, int64_t n_bytes, int64_t* 
   hipStream_t st = as_stream(stream);
   const int64_t nb = ceil_div(n_bytes, kLineBlock);
   Carver c(workspace, ws_bytes);
-  int32_t* cnt = c.take<int32_t>(nb);
-  int32_t* offs = c.take<int32_t>(nb);
-  void* sws = c.take<char>(exclusive_scan_ws_size(nb));
+  const auto [cnt, offs, sws] = scan_ws(c, nb);
   if (!c.ok()) {
     set_error("rs_line_index: workspace too small");
     return RS_E_WORKSPACE;
@@ -289,9 +290,7 @@ extern "C" int32_t rs_vocab_count_masked(const uint64_t* hashes, const uint8_t* 
 
 extern "C" size_t rs_vocab_collect_workspace_size(int64_t capacity) {
   Carver c(nullptr, 0);
-  c.take<int32_t>(capacity);
-  c.take<int32_t>(capacity);
-  c.take<char>(exclusive_scan_ws_size(capacity));
+  scan_ws(c, capacity);
   return c.off + 256;
 }
 
@@ -302,9 +301,7 @@ extern "C" int32_t rs_vocab_collect(const uint64_t* keys, const uint32_t* counts
                                     void* stream) {
   hipStream_t st = as_stream(stream);
   Carver c(workspace, ws_bytes);
-  int32_t* flag = c.take<int32_t>(capacity);
-  int32_t* offs = c.take<int32_t>(capacity);
-  void* sws = c.take<char>(exclusive_scan_ws_size(capacity));
+  const auto [flag, offs, sws] = scan_ws(c, capacity);
   if (!c.ok()) {
     set_error("rs_vocab_collect: workspace too small");
     return RS_E_WORKSPACE;

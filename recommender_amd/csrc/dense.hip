@@ -372,11 +372,6 @@ struct Chain3Args {
   float* p;           // [n0]
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // out[i] = Σ_k M[row(i), k] · v[k] (one wave per output, lanes stride k, fixed butterfly)
 __device__ __forceinline__ void rowdot_wave(const float* M, int ld, int i_row, int n,
                                             const float* v, float* out_i, int lane) {

@@ -17,12 +17,8 @@ namespace rs {
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 // two gates' recurrent sums as one packed pair: v_pk_fma_f32 does both fused multiply-adds in one
 // instruction (each element rounded once, as two fmaf)
-typedef float pk2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ pk2 pk_fma(float a, pk2 b, pk2 c) {
-  return __builtin_elementwise_fma(pk2{a, a}, b, c);
-}
-__device__ __forceinline__ float bcast(float v, int k) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
+__device__ __forceinline__ f2 pk_fma(float a, f2 b, f2 c) {
+  return __builtin_elementwise_fma(f2{a, a}, b, c);
 }
 
 // One gate's recurrent weights in LDS (w(k, j) for lane j, row k; 0 outside H x H) instead of
@@ -74,11 +70,11 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const float* __restrict__ 
   stage_gate<HM>(uh_s, H, [&](int k, int jj) { return U[k * H3 + 2 * H + jj]; });
   if (b >= B) return;
   const bool act = j < H;
-  pk2 uzr[HM];  // (update, reset) recurrent weights of unit j
+  f2 uzr[HM];  // (update, reset) recurrent weights of unit j
 #pragma unroll
   for (int k = 0; k < HM; ++k) {
     const bool ok = act && k < H;
-    uzr[k] = pk2{ok ? U[k * H3 + j] : 0.f, ok ? U[k * H3 + H + j] : 0.f};
+    uzr[k] = f2{ok ? U[k * H3 + j] : 0.f, ok ? U[k * H3 + H + j] : 0.f};
   }
   const float rbz = act ? rb[j] : 0.f, rbr = act ? rb[H + j] : 0.f, rbh = act ? rb[2 * H + j] : 0.f;
   const float* xb = xw + b * (int64_t)L * H3;
@@ -105,11 +101,11 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const float* __restrict__ 
       if (act) out[(b * L + t) * H + j] = h;
       continue;
     }
-    pk2 izr = pk2{0.f, 0.f};
+    f2 izr = f2{0.f, 0.f};
     float ih = 0.f;
 #pragma unroll
     for (int k = 0; k < HM; ++k) {
-      const float hk = bcast(h, k);
+      const float hk = read_lane(h, k);
       izr = pk_fma(hk, uzr[k], izr);
       ih = fmaf(hk, uh_s[k * 64 + j], ih);
     }
@@ -152,11 +148,11 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const float* __restrict__ 
   stage_gate<HM>(wh_s, H, [&](int k, int jj) { return U[jj * H3 + 2 * H + k]; });
   if (b >= B) return;
   const bool act = j < H;
-  pk2 wzr[HM];  // row j of U: (U[j][k], U[j][H + k])
+  f2 wzr[HM];  // row j of U: (U[j][k], U[j][H + k])
 #pragma unroll
   for (int k = 0; k < HM; ++k) {
     const bool ok = act && k < H;
-    wzr[k] = pk2{ok ? U[j * H3 + k] : 0.f, ok ? U[j * H3 + H + k] : 0.f};
+    wzr[k] = f2{ok ? U[j * H3 + k] : 0.f, ok ? U[j * H3 + H + k] : 0.f};
   }
   const uint8_t* mb = mask + b * L;
   const MaskBits mbits(mb, L, j);
@@ -210,12 +206,12 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const float* __restrict__ 
     // three independent 36-deep chains (update / reset gates as one packed pair, candidate)
     // summed at the end, instead of one 108-deep chain: the step's latency in the tail of long
     // histories, where few waves are left to hide it
-    pk2 azr = pk2{0.f, 0.f};
+    f2 azr = f2{0.f, 0.f};
     float ahh = 0.f;
 #pragma unroll
     for (int k = 0; k < HM; ++k) {
-      azr = __builtin_elementwise_fma(pk2{bcast(dpz, k), bcast(dpr, k)}, wzr[k], azr);
-      ahh = fmaf(bcast(dihm, k), wh_s[k * 64 + j], ahh);
+      azr = __builtin_elementwise_fma(f2{read_lane(dpz, k), read_lane(dpr, k)}, wzr[k], azr);
+      ahh = fmaf(read_lane(dihm, k), wh_s[k * 64 + j], ahh);
     }
     const float acc = dh * z + ((azr.x + azr.y) + ahh);
     dh = act ? acc : 0.f;
@@ -273,7 +269,7 @@ __global__ __launch_bounds__(256) void augru_fwd_kernel(const float* __restrict_
     float iu = 0.f, ir = 0.f;
 #pragma unroll
     for (int k = 0; k < HM; ++k) {
-      const float hk = bcast(h, k);
+      const float hk = read_lane(h, k);
       iu = fmaf(hk, ku[k], iu);
       ir = fmaf(hk, kr[k], ir);
     }
@@ -281,7 +277,7 @@ __global__ __launch_bounds__(256) void augru_fwd_kernel(const float* __restrict_
     const float rh = act ? r * h : 0.f;
     float ihh = 0.f;
 #pragma unroll
-    for (int k = 0; k < HM; ++k) ihh = fmaf(bcast(rh, k), kh_s[k * 64 + j], ihh);
+    for (int k = 0; k < HM; ++k) ihh = fmaf(read_lane(rh, k), kh_s[k * 64 + j], ihh);
     const float hh = tanhf(xh + ihh);
     const float ua = u * a;
     const float hn = ua * hh + (1.f - ua) * h;
@@ -320,11 +316,11 @@ __global__ __launch_bounds__(256) void augru_bwd_kernel(const float* __restrict_
   if (b >= B) return;
   const bool act = j < H;
   const int H3 = 3 * H;
-  pk2 kur[HM];  // rows j: (Kuh[j][k], Krh[j][k])
+  f2 kur[HM];  // rows j: (Kuh[j][k], Krh[j][k])
 #pragma unroll
   for (int k = 0; k < HM; ++k) {
     const bool ok = act && k < H;
-    kur[k] = pk2{ok ? Kuh[j * H + k] : 0.f, ok ? Krh[j * H + k] : 0.f};
+    kur[k] = f2{ok ? Kuh[j * H + k] : 0.f, ok ? Krh[j * H + k] : 0.f};
   }
   const uint8_t* mb = mask + b * L;
   const MaskBits mbits(mb, L, j);
@@ -368,15 +364,15 @@ __global__ __launch_bounds__(256) void augru_bwd_kernel(const float* __restrict_
     const float dph = act ? dh * ua * (1.f - hh * hh) : 0.f;
     float drh = 0.f;
 #pragma unroll
-    for (int k = 0; k < HM; ++k) drh = fmaf(bcast(dph, k), kh_s[k * 64 + j], drh);
+    for (int k = 0; k < HM; ++k) drh = fmaf(read_lane(dph, k), kh_s[k * 64 + j], drh);
     const float dr = drh * hp;
     dhp = fmaf(drh, r, dhp);
     const float dpr = act ? dr * r * (1.f - r) : 0.f;
     // update / reset contributions as one packed pair of 36-deep chains (not one 72-deep chain)
-    pk2 aur = pk2{0.f, 0.f};
+    f2 aur = f2{0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < HM; ++k)
-      aur = __builtin_elementwise_fma(pk2{bcast(dpu, k), bcast(dpr, k)}, kur[k], aur);
+      aur = __builtin_elementwise_fma(f2{read_lane(dpu, k), read_lane(dpr, k)}, kur[k], aur);
     dhp = dhp + (aur.x + aur.y);
     if (act) {
       dx[j] = dpu;
@@ -429,8 +425,7 @@ __global__ __launch_bounds__(64) void att_fwd_kernel(const float* __restrict__ h
       mx = fmaxf(mx, acc);
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+  mx = wave_max(mx);
   float sum = 0.f;
 #pragma unroll
   for (int c = 0; c < kAttMaxT; ++c) {
@@ -438,8 +433,7 @@ __global__ __launch_bounds__(64) void att_fwd_kernel(const float* __restrict__ h
     s[c] = t < L ? expf(s[c] - mx) : 0.f;
     sum += s[c];
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+  sum = wave_sum(sum);
 #pragma unroll
   for (int c = 0; c < kAttMaxT; ++c) {
     const int t = lane + 64 * c;
@@ -464,8 +458,7 @@ __global__ __launch_bounds__(256) void att_bwd_kernel(const float* __restrict__ 
     const int t = lane + 64 * c;
     if (t < L) dot += a[b * L + t] * da[b * L + t];
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) dot += __shfl_xor(dot, off);
+  dot = wave_sum(dot);
 #pragma unroll
   for (int c = 0; c < kAttMaxT; ++c) {
     const int t = lane + 64 * c;

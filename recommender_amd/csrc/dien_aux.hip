@@ -28,12 +28,6 @@
 
 namespace rs {
 
-int32_t fold_two_level(const float* part, int nchunks, int N, float* part2, float* out,
-                       hipStream_t st);
-int32_t exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, int32_t* total, void* ws,
-                           size_t ws_bytes, hipStream_t st);
-size_t exclusive_scan_ws_size(int64_t n);
-
 namespace {
 
 constexpr int kBwdBlocksPerCU = 1;

@@ -18,8 +18,6 @@
 
 namespace rs {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 constexpr int kVrTile = 4096;  // mask rows per block of the valid-row list
 
 __global__ __launch_bounds__(256) void vr_count_kernel(const uint8_t* __restrict__ mask, int64_t R,
@@ -73,10 +71,6 @@ __global__ __launch_bounds__(256) void vr_write_kernel(const uint8_t* __restrict
     *count = off_s + wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-__device__ __forceinline__ float rdlane(float v, int k) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
-}
-
 // y[r, n] = b[n] + Σ_k x[r, k]·W[k, n] for the listed rows; K <= KM <= 64, N <= 64·NB.
 // One wave per 32 listed rows (the grid is sized for the capacity R; waves past the count leave
 // before loading anything): W's columns in VGPRs, the rows' x loaded together, x[k] broadcast
@@ -118,7 +112,7 @@ __global__ __launch_bounds__(256) void masked_proj_kernel(const float* __restric
     for (int nb = 0; nb < NB; ++nb) acc[nb] = bb[nb];
 #pragma unroll
     for (int k = 0; k < KM; ++k) {
-      const float xk = rdlane(xr[i], k);
+      const float xk = read_lane(xr[i], k);
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) acc[nb] = fmaf(xk, w[nb][k], acc[nb]);
     }
@@ -215,11 +209,11 @@ __global__ __launch_bounds__(256) void masked_dx_kernel(const float* __restrict_
   for (int i = 0; i < 16; ++i) {
     const int row = __builtin_amdgcn_readlane(rr, i);
     if (row < 0) break;
-    const floatx4* rowp = reinterpret_cast<const floatx4*>(&ds[wave][i][0]);
+    const f4* rowp = reinterpret_cast<const f4*>(&ds[wave][i][0]);
     float acc = 0.f;
 #pragma unroll
     for (int n4 = 0; n4 < NM / 4; ++n4) {
-      const floatx4 v = rowp[n4];
+      const f4 v = rowp[n4];
       acc = fmaf(v[0], w[4 * n4], acc);
       acc = fmaf(v[1], w[4 * n4 + 1], acc);
       acc = fmaf(v[2], w[4 * n4 + 2], acc);
@@ -300,7 +294,7 @@ __global__ __launch_bounds__(1024) void masked_wgrad_kernel(const float* __restr
       if (kk[j] < 0) continue;
       for (int i = 0; i < nr; ++i) {
         const float a = As[i][kk[j]];
-        const floatx4 v = *reinterpret_cast<const floatx4*>(&Ds[i][4 * cq[j]]);
+        const f4 v = *reinterpret_cast<const f4*>(&Ds[i][4 * cq[j]]);
 #pragma unroll
         for (int c = 0; c < 4; ++c) acc[j][c] = fmaf(a, v[c], acc[j][c]);
       }

@@ -26,9 +26,6 @@
 
 namespace rs {
 
-int32_t fold_two_level(const float* part, int nchunks, int N, float* part2, float* out,
-                       hipStream_t st);
-
 namespace {
 
 constexpr int kFwdBlocksPerCU = 3;  // 43 KB of LDS each

@@ -11,16 +11,6 @@
 
 namespace rs {
 
-int32_t exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, int32_t* total, void* ws,
-                           size_t ws_bytes, hipStream_t st);
-size_t exclusive_scan_ws_size(int64_t n);
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
 constexpr int kMaxSide = 16;
 constexpr int kWavesPerBlock = 4;
 
@@ -148,7 +138,6 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void pool_bwd_kernel(
 // Any layout: side row s of example b at side + b * sb + s * ss (MMOE pools its experts' outputs
 // in the [E, B, H] order the batched expert GEMMs leave them). The forward sums in the same order
 // as the scalar kernel (bit-identical); the backward's <g, side_s> folds over the half-wave.
-typedef float pf4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float half_sum(float v) {
 #pragma unroll
   for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, 32);
@@ -178,11 +167,11 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void pool_fwd_vec_kernel(
   }
   if (4 * c >= D) return;
   const float* x = side + b * sb + 4 * c;
-  pf4 v[kMaxSide];
+  f4 v[kMaxSide];
 #pragma unroll
   for (int s = 0; s < kMaxSide; ++s)
-    if (s < S) v[s] = *reinterpret_cast<const pf4*>(x + s * ss);
-  pf4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (s < S) v[s] = *reinterpret_cast<const f4*>(x + s * ss);
+  f4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < kMaxSide; ++s) {
     if (s < S) {
@@ -191,7 +180,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void pool_fwd_vec_kernel(
     }
   }
   if (!wlogits) acc = acc / (float)S;
-  *reinterpret_cast<pf4*>(hidden + b * D + 4 * c) = acc;
+  *reinterpret_cast<f4*>(hidden + b * D + 4 * c) = acc;
 }
 
 __global__ __launch_bounds__(kWave * kWavesPerBlock) void pool_bwd_vec_kernel(
@@ -202,25 +191,25 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void pool_bwd_vec_kernel(
   const int64_t b = ((int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * 2 + (lane >> 5);
   if (b >= B) return;  // a whole half-wave: its shuffles below stay within its own 32 lanes
   const bool on = 4 * c < D;
-  const pf4 gd = on ? *reinterpret_cast<const pf4*>(g + b * D + 4 * c) : pf4{0.f, 0.f, 0.f, 0.f};
+  const f4 gd = on ? *reinterpret_cast<const f4*>(g + b * D + 4 * c) : f4{0.f, 0.f, 0.f, 0.f};
   if (!attn) {
     if (on)
       for (int s = 0; s < S; ++s)
-        *reinterpret_cast<pf4*>(grad_side + b * sb + s * ss + 4 * c) = gd / (float)S;
+        *reinterpret_cast<f4*>(grad_side + b * sb + s * ss + 4 * c) = gd / (float)S;
     return;
   }
   float a[kMaxSide], ga[kMaxSide];
   for (int s = 0; s < S; ++s) a[s] = attn[b * S + s];
-  pf4 v[kMaxSide];
+  f4 v[kMaxSide];
 #pragma unroll
   for (int s = 0; s < kMaxSide; ++s)
-    if (s < S) v[s] = on ? *reinterpret_cast<const pf4*>(side + b * sb + s * ss + 4 * c)
-                         : pf4{0.f, 0.f, 0.f, 0.f};
+    if (s < S) v[s] = on ? *reinterpret_cast<const f4*>(side + b * sb + s * ss + 4 * c)
+                         : f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < kMaxSide; ++s) {
     if (s < S) {
-      if (on) *reinterpret_cast<pf4*>(grad_side + b * sb + s * ss + 4 * c) = a[s] * gd;
-      const pf4 p = gd * v[s];
+      if (on) *reinterpret_cast<f4*>(grad_side + b * sb + s * ss + 4 * c) = a[s] * gd;
+      const f4 p = gd * v[s];
       ga[s] = half_sum((p[0] + p[1]) + (p[2] + p[3]));
     }
   }
@@ -261,25 +250,25 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void pool_fwd_multi_kernel(
   // side 0 / column 0) and masked where used; guarded per element, the compiler waited for each
   // (tools/isa_wait_audit.py)
   const int cc = on ? 4 * c : 0;
-  pf4 v[kMaxSide], bb[kMaxSide];
+  f4 v[kMaxSide], bb[kMaxSide];
 #pragma unroll
   for (int s = 0; s < kMaxSide; ++s)
-    v[s] = *reinterpret_cast<const pf4*>(side + b * sb + (s < S ? s : 0) * ss + cc);
+    v[s] = *reinterpret_cast<const f4*>(side + b * sb + (s < S ? s : 0) * ss + cc);
   if (sbias) {
 #pragma unroll
     for (int s = 0; s < kMaxSide; ++s)
-      bb[s] = *reinterpret_cast<const pf4*>(sbias + (s < S ? s : 0) * D + cc);
+      bb[s] = *reinterpret_cast<const f4*>(sbias + (s < S ? s : 0) * D + cc);
   }
 #pragma unroll
   for (int s = 0; s < kMaxSide; ++s)
-    if (!(s < S && on)) v[s] = pf4{0.f, 0.f, 0.f, 0.f};
+    if (!(s < S && on)) v[s] = f4{0.f, 0.f, 0.f, 0.f};
   if (sbias && on) {
 #pragma unroll
     for (int s = 0; s < kMaxSide; ++s) {
       if (s < S) {
-        const pf4 z = v[s] + bb[s];
-        v[s] = pf4{fmaxf(z[0], 0.f), fmaxf(z[1], 0.f), fmaxf(z[2], 0.f), fmaxf(z[3], 0.f)};
-        *reinterpret_cast<pf4*>(side + b * sb + s * ss + 4 * c) = v[s];
+        const f4 z = v[s] + bb[s];
+        v[s] = f4{fmaxf(z[0], 0.f), fmaxf(z[1], 0.f), fmaxf(z[2], 0.f), fmaxf(z[3], 0.f)};
+        *reinterpret_cast<f4*>(side + b * sb + s * ss + 4 * c) = v[s];
       }
     }
   }
@@ -300,11 +289,11 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void pool_fwd_multi_kernel(
       for (int s = 0; s < S; ++s)
         if (s == c) pt.attn[t][b * S + s] = a[s];
     }
-    pf4 acc = {0.f, 0.f, 0.f, 0.f};
+    f4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < kMaxSide; ++s)
       if (s < S) acc += a[s] * v[s];
-    if (on) *reinterpret_cast<pf4*>(pt.hidden[t] + b * D + 4 * c) = acc;
+    if (on) *reinterpret_cast<f4*>(pt.hidden[t] + b * D + 4 * c) = acc;
   }
 }
 
@@ -315,22 +304,22 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void pool_bwd_multi_kernel(
   const int64_t b = ((int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * 2 + (lane >> 5);
   if (b >= B) return;  // a whole half-wave: its shuffles stay within its own 32 lanes
   const bool on = 4 * c < D;
-  pf4 v[kMaxSide], gs[kMaxSide];
+  f4 v[kMaxSide], gs[kMaxSide];
 #pragma unroll
   for (int s = 0; s < kMaxSide; ++s)
-    if (s < S) v[s] = on ? *reinterpret_cast<const pf4*>(side + b * sb + s * ss + 4 * c)
-                         : pf4{0.f, 0.f, 0.f, 0.f};
+    if (s < S) v[s] = on ? *reinterpret_cast<const f4*>(side + b * sb + s * ss + 4 * c)
+                         : f4{0.f, 0.f, 0.f, 0.f};
   for (int t = 0; t < pt.T; ++t) {
-    const pf4 gd = on ? *reinterpret_cast<const pf4*>(pt.g[t] + b * D + 4 * c)
-                      : pf4{0.f, 0.f, 0.f, 0.f};
+    const f4 gd = on ? *reinterpret_cast<const f4*>(pt.g[t] + b * D + 4 * c)
+                      : f4{0.f, 0.f, 0.f, 0.f};
     float a[kMaxSide], ga[kMaxSide];
     for (int s = 0; s < S; ++s) a[s] = pt.attn[t][b * S + s];
 #pragma unroll
     for (int s = 0; s < kMaxSide; ++s) {
       if (s < S) {
-        const pf4 q = a[s] * gd;
+        const f4 q = a[s] * gd;
         gs[s] = t == 0 ? q : gs[s] + q;
-        const pf4 p = gd * v[s];
+        const f4 p = gd * v[s];
         ga[s] = half_sum((p[0] + p[1]) + (p[2] + p[3]));
       }
     }
@@ -342,7 +331,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void pool_bwd_multi_kernel(
   if (on) {
 #pragma unroll
     for (int s = 0; s < kMaxSide; ++s)
-      if (s < S) *reinterpret_cast<pf4*>(grad_side + b * sb + s * ss + 4 * c) = gs[s];
+      if (s < S) *reinterpret_cast<f4*>(grad_side + b * sb + s * ss + 4 * c) = gs[s];
   }
 }
 
@@ -686,12 +675,18 @@ static int32_t skipgram_slots(int32_t len, int32_t window) {
   return k;
 }
 
+// workspace of rs_skipgram_pairs over n slots (a braced list: the takes run in the order written)
+struct SkipgramWs {
+  int32_t *flag, *offs;
+  void* sws;
+};
+static SkipgramWs skipgram_ws(Carver& c, int64_t n) {
+  return {c.take<int32_t>(n), c.take<int32_t>(n), c.take<char>(exclusive_scan_ws_size(n < 1 ? 1 : n))};
+}
+
 extern "C" size_t rs_skipgram_workspace_size(int32_t n_traces, int32_t len, int32_t window) {
-  const int64_t n = (int64_t)n_traces * skipgram_slots(len, window);
   Carver c(nullptr, 0);
-  c.take<int32_t>(n);
-  c.take<int32_t>(n);
-  c.take<char>(exclusive_scan_ws_size(n < 1 ? 1 : n));
+  skipgram_ws(c, (int64_t)n_traces * skipgram_slots(len, window));
   return c.off + 256;
 }
 
@@ -708,9 +703,7 @@ extern "C" int32_t rs_skipgram_pairs(const int32_t* traces, int32_t n_traces, in
     return RS_OK;
   }
   Carver c(workspace, ws_bytes);
-  int32_t* flag = c.take<int32_t>(n);
-  int32_t* offs = c.take<int32_t>(n);
-  void* sws = c.take<char>(exclusive_scan_ws_size(n));
+  const auto [flag, offs, sws] = skipgram_ws(c, n);
   if (!c.ok()) {
     set_error("rs_skipgram_pairs: workspace too small");
     return RS_E_WORKSPACE;

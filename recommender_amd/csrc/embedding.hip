@@ -14,76 +14,9 @@
 // therefore fixed by the sorted order alone (oracle/embedding.py:segment_sum_tiled).
 #include <cstdlib>
 
-#include "common.hpp"
+#include "row_io.hpp"
 
 namespace rs {
-
-int32_t radix_sort_pairs(uint32_t*, int32_t*, uint32_t*, int32_t*, int64_t, int64_t, void*, size_t,
-                         hipStream_t);
-size_t radix_sort_ws_size(int64_t);
-int32_t exclusive_scan_i32(const int32_t*, int32_t*, int64_t, int32_t*, void*, size_t, hipStream_t);
-size_t exclusive_scan_ws_size(int64_t);
-
-// ---- vector row I/O ------------------------------------------------------------------
-template <int VEC>
-struct RowIO;
-template <>
-struct RowIO<4> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-    float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-};
-// a read-once stream (the walk's gradient rows): non-temporal, so it does not evict the
-// table rows and tile partials that are read again
-template <int VEC>
-__device__ __forceinline__ void load_stream(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p));
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    RowIO<VEC>::load(p, v);
-  }
-}
-template <>
-struct RowIO<2> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[2]) {
-    float2 t = *reinterpret_cast<const float2*>(p);
-    v[0] = t.x; v[1] = t.y;
-  }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[2]) {
-    *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-  }
-};
-template <>
-struct RowIO<1> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[1]) { v[0] = *p; }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[1]) { *p = v[0]; }
-};
-
-struct RowGeom {
-  int vec, lpr_log2, cpl;
-};
-
-static RowGeom row_geom(int dim, const void* const* ptrs, int nptr) {
-  int vec = (dim % 4 == 0) ? 4 : (dim % 2 == 0 ? 2 : 1);
-  // downgrade the vector width if any base pointer is not aligned for it
-  for (int i = 0; i < nptr; ++i) {
-    uintptr_t a = reinterpret_cast<uintptr_t>(ptrs[i]);
-    while (vec > 1 && (a % (vec * 4)) != 0) vec >>= 1;
-  }
-  int chunks = dim / vec;
-  int lpr = 1, l2 = 0;
-  while (lpr < chunks && lpr < 64) { lpr <<= 1; ++l2; }
-  int cpl = (chunks + lpr - 1) / lpr;
-  int c = 1;
-  while (c < cpl) c <<= 1;
-  return {vec, l2, c};
-}
 
 // ---- a-1: gather ----------------------------------------------------------------------
 template <int VEC, int CPL>
@@ -133,7 +66,7 @@ __global__ __launch_bounds__(256) void gather_kernel(const float* __restrict__ t
       }
     }
   }
-  if (__any(oob) && (threadIdx.x & 63) == 0) flag_oob(err_flag);
+  flag_oob_wave(oob, err_flag);
 }
 
 // Narrow rows whose width is not a multiple of 4 floats (ESMM / MMOE's D = 18: 72-B rows, 8-B
@@ -160,7 +93,7 @@ __global__ __launch_bounds__(256) void gather_flat2_kernel(const float* __restri
                             : make_float2(0.f, 0.f);
     *reinterpret_cast<float2*>(out + 2 * q) = v;
   }
-  if (__any(oob) && (threadIdx.x & 63) == 0) flag_oob(err_flag);
+  flag_oob_wave(oob, err_flag);
 }
 
 // ---- a-2: segmented sum + apply -------------------------------------------------------
@@ -1263,14 +1196,7 @@ static int32_t launch_segments(int opt, const uint32_t* keys, const int32_t* pos
   const int gpb = 256 >> geom.lpr_log2;
   const int64_t blocks = ceil_div(n_tiles, gpb);
   if (blocks == 0) return RS_OK;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  const int64_t walk_blocks = std::min<int64_t>(blocks, (int64_t)cus * kApplyBlocksPerCU);
+  const int64_t walk_blocks = std::min<int64_t>(blocks, (int64_t)device_cus() * kApplyBlocksPerCU);
 #ifndef RS_NO_T32
   const bool t32 = geom.vec == 4 && geom.cpl == 1 && geom.lpr_log2 == 5 && RS_DEDUP_TILE == 32;
 #else
@@ -1385,17 +1311,20 @@ extern "C" int32_t rs_embedding_fwd_strided(const float* table, int64_t n_rows, 
   return RS_OK;
 }
 
+// the walk's scratch, carved into a: tile partials + level-1 chunk sums, each [n_tiles][2][dim],
+// + one flag byte per tile; the carver is left 256-aligned
+static void take_partials(Carver& c, int64_t n_ids, int32_t dim, ApplyArgs& a) {
+  const size_t n_tiles = ceil_div(n_ids, RS_DEDUP_TILE);
+  a.partial = c.take<float>(n_tiles * 2 * dim);
+  a.chunk = c.take<float>(n_tiles * 2 * dim);
+  a.tile_flags = c.take<uint8_t>(n_tiles);
+  c.off = align_up(c.off, 256);
+}
 static size_t partial_bytes(int64_t n_ids, int32_t dim) {
-  // tile partials + level-1 chunk sums, each [n_tiles][2][dim], + one flag byte per tile
-  return 2 * align_up((size_t)ceil_div(n_ids, RS_DEDUP_TILE) * 2 * dim * sizeof(float), 256) +
-         align_up((size_t)ceil_div(n_ids, RS_DEDUP_TILE), 256);
-}
-static uint8_t* flags_of(float* partial, int64_t n_ids, int32_t dim) {
-  return reinterpret_cast<uint8_t*>(partial) +
-         2 * align_up((size_t)ceil_div(n_ids, RS_DEDUP_TILE) * 2 * dim * sizeof(float), 256);
-}
-static float* chunk_of(float* partial, int64_t n_ids, int32_t dim) {
-  return partial + align_up((size_t)ceil_div(n_ids, RS_DEDUP_TILE) * 2 * dim * sizeof(float), 256) / 4;
+  Carver c(nullptr, 0);
+  ApplyArgs a{};
+  take_partials(c, n_ids, dim, a);
+  return c.off;
 }
 
 extern "C" size_t rs_dedup_workspace_size(int64_t n_ids, int32_t dim) {
@@ -1474,7 +1403,8 @@ extern "C" int32_t rs_embedding_dedup_grad_mapped_range(
   }
   hipStream_t st = as_stream(stream);
   Carver c(workspace, ws_bytes);
-  float* partial = c.take<float>(partial_bytes(n_ids, dim) / 4);
+  ApplyArgs a{};
+  take_partials(c, n_ids, dim, a);
   int32_t* seg = c.take<int32_t>(n_ids);
   void* scan_ws = c.take<char>(exclusive_scan_ws_size(n_ids));
   int blocks = (int)std::min<int64_t>(ceil_div(n_ids, 256), 4096);
@@ -1486,11 +1416,7 @@ extern "C" int32_t rs_embedding_dedup_grad_mapped_range(
     int32_t s = exclusive_scan_i32(seg, seg, n_ids, nullptr, scan_ws, exclusive_scan_ws_size(n_ids), st);
     if (s) return s;
   }
-  ApplyArgs a{};
   a.dim = dim;
-  a.partial = partial;
-  a.chunk = chunk_of(partial, n_ids, dim);
-  a.tile_flags = flags_of(partial, n_ids, dim);
   a.uniq_grad = uniq_grad;
   a.uniq_rows = uniq_rows;
   a.seg_excl = seg;
@@ -1521,9 +1447,8 @@ extern "C" int32_t rs_embedding_grad_dense(const uint32_t* sorted_rows, const in
   ApplyArgs a{};
   a.table = dense;
   a.dim = dim;
-  a.partial = static_cast<float*>(workspace);
-  a.chunk = chunk_of(a.partial, n_ids, dim);
-  a.tile_flags = flags_of(a.partial, n_ids, dim);
+  Carver c(workspace, ws_bytes);
+  take_partials(c, n_ids, dim, a);
   const void* ptrs[2] = {grad_out, dense};
   RowGeom geom = row_geom(dim, ptrs, 2);
   return launch_segments(OPT_DENSE, sorted_rows, sorted_pos, n_ids, n_rows, grad_out, a, geom, st);
@@ -1566,9 +1491,8 @@ extern "C" int32_t rs_embedding_grad_dense_segs(const uint32_t* sorted_rows,
   }
   a.table = dense;
   a.dim = dim;
-  a.partial = static_cast<float*>(workspace);
-  a.chunk = chunk_of(a.partial, n_ids, dim);
-  a.tile_flags = flags_of(a.partial, n_ids, dim);
+  Carver c(workspace, ws_bytes);
+  take_partials(c, n_ids, dim, a);
   ptrs[np++] = dense;
   RowGeom geom = row_geom(dim, ptrs, np);
   // the 128-wide group / tile32 walks address rows as grad + p * dim: keep them off this path
@@ -1632,9 +1556,8 @@ extern "C" int32_t rs_embedding_apply_scaled(int32_t opt, float* table, float* m
   a.bitmap = adagrad ? nullptr : touched_bitmap;
   a.row_scale = row_scale;
   a.scale_group = scale_group;
-  a.partial = static_cast<float*>(workspace);
-  a.chunk = chunk_of(a.partial, n_ids, dim);
-  a.tile_flags = flags_of(a.partial, n_ids, dim);
+  Carver c(workspace, ws_bytes);
+  take_partials(c, n_ids, dim, a);
   // the row-wise accumulator is one float per row, never moved as a vector; Adagrad ignores v
   const void* ptrs[4] = {table, grad_out, m && opt != RS_OPT_ROWWISE_ADAGRAD ? m : table,
                          v && !adagrad ? v : table};

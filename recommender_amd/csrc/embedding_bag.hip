@@ -11,54 +11,10 @@
 // No atomics except the error flag's OR.
 #include <algorithm>
 
-#include "common.hpp"
+#include "row_io.hpp"
 
 namespace rs {
 namespace {
-
-template <int VEC>
-struct BagIO;
-template <>
-struct BagIO<4> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-    float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-};
-template <>
-struct BagIO<2> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[2]) {
-    float2 t = *reinterpret_cast<const float2*>(p);
-    v[0] = t.x; v[1] = t.y;
-  }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[2]) {
-    *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-  }
-};
-template <>
-struct BagIO<1> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[1]) { v[0] = *p; }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[1]) { *p = v[0]; }
-};
-
-struct BagGeom {
-  int vec, lpr_log2, chunks;  // chunks: column chunks of (lanes * vec) floats per row
-};
-
-// embedding.hip's row_geom: the widest vector every base pointer and row stride allows, the
-// smallest power-of-two lane group that covers the row (64 lanes at most)
-BagGeom bag_geom(int dim, const uintptr_t* addrs, int n) {
-  int vec = (dim % 4 == 0) ? 4 : (dim % 2 == 0 ? 2 : 1);
-  for (int i = 0; i < n; ++i)
-    while (vec > 1 && (addrs[i] % (vec * 4)) != 0) vec >>= 1;
-  const int per_row = dim / vec;
-  int lpr = 1, l2 = 0;
-  while (lpr < per_row && lpr < 64) { lpr <<= 1; ++l2; }
-  return {vec, l2, (per_row + lpr - 1) / lpr};
-}
 
 // [s, e) of bag b; a reversed range or one that leaves [0, n_ids] is empty and reported
 __device__ __forceinline__ bool bag_range(const int64_t* __restrict__ offsets, int64_t b,
@@ -152,7 +108,7 @@ __global__ __launch_bounds__(256) void bag_fwd_kernel(
           live[u] = p0 + u < e && (!valid || vl[u] != 0);
           in[u] = id[u] >= 0 && id[u] < card;
           const int64_t r = (live[u] && in[u]) ? lo + id[u] : 0;
-          BagIO<VEC>::load(table + r * dim + colc, v[u]);
+          RowIO<VEC>::load(table + r * dim + colc, v[u]);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -174,12 +130,12 @@ __global__ __launch_bounds__(256) void bag_fwd_kernel(
 #pragma unroll
           for (int k = 0; k < VEC; ++k) acc[k] = count > 0 ? __fdiv_rn(acc[k], n) : 0.f;
         }
-        BagIO<VEC>::store(out + b * out_ld + col, acc);
+        RowIO<VEC>::store(out + b * out_ld + col, acc);
       }
     }
     if (bag_scale && gl == 0) bag_scale[b] = count > 0 ? __fdiv_rn(1.f, (float)count) : 0.f;
   }
-  if (__any(bad) && (threadIdx.x & 63) == 0) flag_oob(err_flag);
+  flag_oob_wave(bad, err_flag);
 }
 
 __global__ __launch_bounds__(256) void bag_remap_kernel(const int32_t* __restrict__ sorted_pos,
@@ -214,7 +170,7 @@ __global__ __launch_bounds__(256) void bag_expand_kernel(
       if (col >= dim) continue;
       float g[VEC];
       if (b >= 0) {
-        BagIO<VEC>::load(dout + b * dout_ld + col, g);
+        RowIO<VEC>::load(dout + b * dout_ld + col, g);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
           if (bag_scale) g[k] = __fmul_rn(sc, g[k]);
@@ -224,7 +180,7 @@ __global__ __launch_bounds__(256) void bag_expand_kernel(
 #pragma unroll
         for (int k = 0; k < VEC; ++k) g[k] = 0.f;
       }
-      BagIO<VEC>::store(grad_rows + p * dim + col, g);
+      RowIO<VEC>::store(grad_rows + p * dim + col, g);
     }
   }
 }
@@ -263,9 +219,8 @@ extern "C" int32_t rs_embedding_bag_fwd(const float* table, int64_t n_rows, int3
   if (int32_t st = check_layout(offsets, n_ids, n_bags, bag_len)) return st;
   if (n_bags == 0) return RS_OK;
   RS_CHECK_ARG(table && out && (n_ids == 0 || ids), "null pointer");
-  const uintptr_t addrs[3] = {reinterpret_cast<uintptr_t>(table), reinterpret_cast<uintptr_t>(out),
-                              (uintptr_t)out_ld * 4};
-  const BagGeom g = bag_geom(dim, addrs, 3);
+  const void* ptrs[3] = {table, out, reinterpret_cast<const void*>((uintptr_t)out_ld * 4)};
+  const RowGeom g = row_geom(dim, ptrs, 3);
   const int gpb = 256 >> g.lpr_log2;
   const int blocks = (int)std::min<int64_t>(ceil_div(n_bags, gpb), 256 * 64);
   hipStream_t st = as_stream(stream);
@@ -312,9 +267,9 @@ extern "C" int32_t rs_embedding_bag_expand_grad(const float* dout, int64_t dout_
   if (int32_t st = check_layout(offsets, n_ids, n_bags, bag_len)) return st;
   if (n_ids == 0) return RS_OK;
   RS_CHECK_ARG(grad_rows && (n_bags == 0 || dout), "null pointer");
-  const uintptr_t addrs[3] = {reinterpret_cast<uintptr_t>(dout ? dout : grad_rows),
-                              reinterpret_cast<uintptr_t>(grad_rows), (uintptr_t)dout_ld * 4};
-  const BagGeom g = bag_geom(dim, addrs, 3);
+  const void* ptrs[3] = {dout ? dout : grad_rows, grad_rows,
+                         reinterpret_cast<const void*>((uintptr_t)dout_ld * 4)};
+  const RowGeom g = row_geom(dim, ptrs, 3);
   const int gpb = 256 >> g.lpr_log2;
   const int blocks = (int)std::min<int64_t>(ceil_div(n_ids, gpb), 256 * 64);
   hipStream_t st = as_stream(stream);

@@ -21,7 +21,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.hpp"
+#include "row_io.hpp"
 
 namespace rs {
 namespace {
@@ -89,17 +89,6 @@ __device__ __forceinline__ void store_cols(float* __restrict__ o, int col0, int 
 }
 
 constexpr int kHeader = 8;  // the readers' piece 0 starts at the codes
-
-struct Q8Geom {
-  int lpr_log2, chunks;
-};
-
-// the smallest power-of-two lane group that covers `pieces` (64 lanes at most)
-Q8Geom q8_geom(int64_t pieces) {
-  int lpr = 1, l2 = 0;
-  while (lpr < pieces && lpr < 64) { lpr <<= 1; ++l2; }
-  return {l2, (int)((pieces + lpr - 1) / lpr)};
-}
 
 __device__ __forceinline__ bool nonfinite(float x) {
   return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;
@@ -353,7 +342,7 @@ __global__ __launch_bounds__(256) void q8_bag_kernel(
     }
     if (bag_scale && gl == 0) bag_scale[b] = count > 0 ? __fdiv_rn(1.f, (float)count) : 0.f;
   }
-  if (__any(bad) && (threadIdx.x & 63) == 0) flag_oob(err_flag);
+  flag_oob_wave(bad, err_flag);
 }
 
 // q_ld >= 8 + dim, a multiple of 4; the table 4-byte aligned (the header is two floats)
@@ -380,7 +369,7 @@ int32_t q8_lookup(const uint8_t* qtable, int64_t n_rows, int32_t dim, int64_t q_
                   int32_t n_slots, float* out, int64_t out_ld, int32_t* err_flag,
                   hipStream_t st) {
   const bool o4 = out_vec4(out, out_ld);
-  const Q8Geom g = q8_geom(((int64_t)dim + 3) / 4);
+  const LaneGroup g = lane_group(((int64_t)dim + 3) / 4);
   const int gpb = 256 >> g.lpr_log2;
   const int blocks = (int)std::min<int64_t>(ceil_div(n_ids, gpb * 4), 256 * 16);
 #define RS_Q8_LOOKUP(O4, T, IDENT)                                                              \
@@ -419,7 +408,7 @@ extern "C" int32_t rs_quantize_rows_q8(const float* table, int64_t ld, int64_t n
   if (n_rows == 0) return RS_OK;
   RS_CHECK_ARG(table && qtable, "null pointer");
   const bool wide = q8_wide(qtable, q_ld);
-  const Q8Geom g = q8_geom(q_ld / (wide ? 16 : 4));
+  const LaneGroup g = lane_group(q_ld / (wide ? 16 : 4));
   const int gpb = 256 >> g.lpr_log2;
   const int blocks = (int)std::min<int64_t>(ceil_div(n_rows, gpb), 256 * 64);
   hipStream_t st = as_stream(stream);
@@ -490,7 +479,7 @@ extern "C" int32_t rs_embedding_bag_q8_fwd(const uint8_t* qtable, int64_t q_ld, 
   const bool o4 = out_vec4(out, out_ld);
   // 8-byte pieces when every row's codes start 8-byte aligned
   const int pw = (reinterpret_cast<uintptr_t>(qtable) | (uintptr_t)q_ld) % 8 == 0 ? 8 : 4;
-  const Q8Geom g = q8_geom(((int64_t)dim + pw - 1) / pw);
+  const LaneGroup g = lane_group(((int64_t)dim + pw - 1) / pw);
   const int gpb = 256 >> g.lpr_log2;
   const int blocks = (int)std::min<int64_t>(ceil_div(n_bags, gpb), 256 * 64);
   hipStream_t st = as_stream(stream);

@@ -26,15 +26,9 @@
 //   wgrad    dW = xᵀ·dz     ta 1, tb 0, K = the batch: split into `splits` K ranges written as
 //            partials and folded in split order (deterministic).
 // Batched (MMOE's experts): blockIdx.z = batch · splits + split, with per-batch strides.
-#include "common.hpp"
+#include "mfma_x3.hpp"
 
 namespace rs {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
 
 constexpr int kBM = 128, kBN = 128, kBK = 32;
 constexpr int kPlane = 128 * kBK * 2;  // bytes of one part plane of a 128-row tile
@@ -52,11 +46,8 @@ __device__ __forceinline__ int swz_off(int row, int chunk) {
 __device__ __forceinline__ void split4(const f4& x, bf4& h, bf4& m, bf4& l) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const f2 v = f2{x[2 * j], x[2 * j + 1]};
-    const bf2 hp = __builtin_convertvector(v, bf2);
-    const f2 r1 = v - __builtin_convertvector(hp, f2);
-    const bf2 mp = __builtin_convertvector(r1, bf2);
-    const bf2 lp = __builtin_convertvector(r1 - __builtin_convertvector(mp, f2), bf2);
+    bf2 hp, mp, lp;
+    split_pair(f2{x[2 * j], x[2 * j + 1]}, hp, mp, lp);
     h[2 * j] = hp[0];
     h[2 * j + 1] = hp[1];
     m[2 * j] = mp[0];
@@ -64,16 +55,6 @@ __device__ __forceinline__ void split4(const f4& x, bf4& h, bf4& m, bf4& l) {
     l[2 * j] = lp[0];
     l[2 * j + 1] = lp[1];
   }
-}
-
-__device__ __forceinline__ f4 mfma6(const bf8& ah, const bf8& am, const bf8& al, const bf8& bh,
-                                    const bf8& bm, const bf8& bl, f4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
 }
 
 // One operand's 128 x 32 slice for this K-step, 4 float4 per thread.

@@ -22,17 +22,9 @@
 #include <tuple>
 #include <type_traits>
 
-#include "common.hpp"
+#include "mfma_x3.hpp"
 
 namespace rs {
-
-// fixed two-level fold of nchunks partial rows [N] into out[N] (csrc/dense.hip); part2 holds
-// 32 x N floats of scratch
-int32_t fold_two_level(const float* part, int nchunks, int N, float* part2, float* out,
-                       hipStream_t st);
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 struct InterMode {
   int self_interaction;
@@ -196,7 +188,7 @@ __global__ __launch_bounds__(256) void inter_fwd_mfma(Src src, int64_t batch, in
     a0[t] = p0 ? *reinterpret_cast<const float4*>(p0 + col) : make_float4(0.f, 0.f, 0.f, 0.f);
     a1[t] = p1 ? *reinterpret_cast<const float4*>(p1 + col) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  floatx4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = c00, c11 = c00;
+  f4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = c00, c11 = c00;
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const float x0[4] = {a0[t].x, a0[t].y, a0[t].z, a0[t].w};
@@ -293,7 +285,7 @@ __global__ __launch_bounds__(256) void inter_fwd_mfma(Src src, int64_t batch, in
       for (int kk = 0; kk < 8; ++kk) bv[kk] = xt[4 * kk + g][r];
       __builtin_amdgcn_s_waitcnt(0xc07f);  // every read done before the next tile's writes
       __builtin_amdgcn_wave_barrier();
-      floatx4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
+      f4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
 #pragma unroll
       for (int kk = 0; kk < 8; ++kk) {
         d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(sa[0][kk], bv[kk], d0, 0, 0, 0);
@@ -379,7 +371,7 @@ __global__ __launch_bounds__(256) void inter_bwd_mfma(Src src, int64_t batch, in
     const int k = 2 * s + h;
     sa[s] = (r < F && k < F) ? m_at(r, k) + m_at(k, r) : 0.f;
   }
-  floatx16 acc[NTILE];
+  f32x16 acc[NTILE];
 #pragma unroll
   for (int c = 0; c < NTILE; ++c)
 #pragma unroll
@@ -445,16 +437,12 @@ constexpr int kPipeEPW = 16;  // upper bound; the launch sizes it to the occupan
 #define RS_PIPE_ROUNDS 2
 #endif
 constexpr int kPipeRounds = RS_PIPE_ROUNDS;
-static int pipe_epw_uncached(const void* kernel, int dev, int64_t batch, int rounds) {
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      cus < 1)
-    cus = 256;
+static int pipe_epw_uncached(const void* kernel, int64_t batch, int rounds) {
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess ||
       per_cu < 1)
     per_cu = 1;
-  const int64_t slots = (int64_t)cus * per_cu * 4 * rounds;  // waves over all rounds
+  const int64_t slots = (int64_t)device_cus() * per_cu * 4 * rounds;  // waves over all rounds
   const int64_t e = ceil_div(batch, slots);
   return (int)(e < 1 ? 1 : (e > 64 ? 64 : e));
 }
@@ -472,13 +460,13 @@ static int pipe_epw(const void* kernel, int64_t batch, int rounds = kPipeRounds)
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
   }
-  const int e = pipe_epw_uncached(kernel, dev, batch, rounds);
+  const int e = pipe_epw_uncached(kernel, batch, rounds);
   std::lock_guard<std::mutex> lk(mu);
   cache[key] = e;
   return e;
 }
 
-typedef __attribute__((address_space(1))) const floatx4 gfloatx4;
+typedef __attribute__((address_space(1))) const f4 gfloatx4;
 typedef __attribute__((address_space(1))) const float gfloat;
 
 // a zero row in global memory: absent / out-of-table rows are gathered from here, so the
@@ -531,7 +519,7 @@ __global__ __launch_bounds__(256) void dlrm_bwd_pipe(GatherSrc src, int64_t batc
   float xv[KS][NTILE];
   auto load_rows = [&](const float* mine, int s) {
     const float* xr = shfl_ptr(mine, 2 * s + h);
-    const floatx4 t = *(gfloatx4*)(xr + NTILE * r);  // global_load_dwordx4 (not flat)
+    const f4 t = *(gfloatx4*)(xr + NTILE * r);  // global_load_dwordx4 (not flat)
     xv[s][0] = t[0];
     xv[s][1] = t[1];
     xv[s][2] = t[2];
@@ -590,7 +578,7 @@ __global__ __launch_bounds__(256) void dlrm_bwd_pipe(GatherSrc src, int64_t batc
       sa[s] = gs[j1] + gs[j2];
     }
     // (2) dX = S·X; each k-step's registers are refilled with b+1's rows right behind it
-    floatx16 acc[NTILE];
+    f32x16 acc[NTILE];
 #pragma unroll
     for (int c = 0; c < NTILE; ++c)
 #pragma unroll
@@ -714,7 +702,7 @@ __global__ __launch_bounds__(256) void dlrm_fwd_dx_pipe(GatherSrc src, int64_t b
     if (lane < S) return id_ok ? src.table + (lo + id) * D : kZeroRow;
     return (lane == S && live) ? src.dense + (b < last ? b : first) * D : kZeroRow;
   };
-  floatx4 a0[NT], a1[NT];
+  f4 a0[NT], a1[NT];
   float dnv[2];
   auto gather = [&](const float* mine, int64_t b) {
     const float* p0 = shfl_ptr(mine, r);
@@ -741,7 +729,7 @@ __global__ __launch_bounds__(256) void dlrm_fwd_dx_pipe(GatherSrc src, int64_t b
     const float* nxt = row_of(b + 1, id_next);
     id_next = raw_id(b + 2);
     // (1) Z = X·Xᵀ (three 16x16 blocks), as inter_fwd_mfma
-    floatx4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = c00, c11 = c00;
+    f4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = c00, c11 = c00;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
@@ -754,8 +742,8 @@ __global__ __launch_bounds__(256) void dlrm_fwd_dx_pipe(GatherSrc src, int64_t b
     // (2) X(b) → LDS rows 0..27 (rows >= F are zeros and never read back as U)
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      *reinterpret_cast<floatx4*>(&X[r * kDxLdx + 16 * t + 4 * g]) = a0[t];
-      if (16 + r < kDxRows) *reinterpret_cast<floatx4*>(&X[(16 + r) * kDxLdx + 16 * t + 4 * g]) = a1[t];
+      *reinterpret_cast<f4*>(&X[r * kDxLdx + 16 * t + 4 * g]) = a0[t];
+      if (16 + r < kDxRows) *reinterpret_cast<f4*>(&X[(16 + r) * kDxLdx + 16 * t + 4 * g]) = a1[t];
     }
     float dn_cur[2] = {dnv[0], dnv[1]};
     // (3) the registers are free: X(b+1) loads fly behind the rest of this example
@@ -808,7 +796,7 @@ __global__ __launch_bounds__(256) void dlrm_fwd_dx_pipe(GatherSrc src, int64_t b
       float bv[KK];
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk) bv[kk] = X[(4 * kk + g) * kDxLdx + 16 * t + r];
-      floatx4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
+      f4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk) {
         d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(sa[0][kk], bv[kk], d0, 0, 0, 0);
@@ -831,12 +819,12 @@ __global__ __launch_bounds__(256) void dlrm_fwd_dx_pipe(GatherSrc src, int64_t b
     for (int s2 = 0; s2 < kDxRows / 2; ++s2) {
       // rows past S are clamped to S: both halves then store the same bottom row
       const int i = 2 * s2 + h < S ? 2 * s2 + h : S;
-      floatx4 v = *reinterpret_cast<const floatx4*>(&X[i * kDxLdx + 4 * r32]);
+      f4 v = *reinterpret_cast<const f4*>(&X[i * kDxLdx + 4 * r32]);
       const bool emb = i < S;
 #pragma unroll
       for (int c = 0; c < 4; ++c) v[c] = emb ? v[c] : v[c] + qdn[c];  // + the concat pass-through
       float* dst = emb ? de + i * D : hd.dxu_dense + b * D;
-      *reinterpret_cast<floatx4*>(dst + 4 * r32) = v;
+      *reinterpret_cast<f4*>(dst + 4 * r32) = v;
     }
     __builtin_amdgcn_wave_barrier();  // the next example's LDS writes follow these reads
   }
@@ -863,21 +851,13 @@ __global__ __launch_bounds__(256) void dlrm_fwd_dx_pipe(GatherSrc src, int64_t b
 // materialised. Per-wave sums (examples in order) are folded per block in wave order and written
 // as one partial row [kTrainM] per block; rs_dlrm_train_fold folds the blocks in a fixed order.
 // ---------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// x = h + m + l with h, m, l bf16 (v_cvt_pk_bf16_f32, round to nearest): the two residuals are
-// exact in fp32 and l carries x's bits below 2^-16 |x| to 2^-24 |x|. lo / hi: elements 0-3 / 4-7.
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split3(const floatx4& lo, const floatx4& hi, bf16x8& h, bf16x8& m,
-                                       bf16x8& l) {
+// eight fp32 values -> their three bf16 parts (split_pair). lo / hi: elements 0-3 / 4-7.
+__device__ __forceinline__ void split3(const f4& lo, const f4& hi, bf8& h, bf8& m,
+                                       bf8& l) {
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {  // in pairs: one v_cvt_pk_bf16_f32 and one v_pk_add_f32 each
-    const floatx2 x = j < 2 ? floatx2{lo[2 * j], lo[2 * j + 1]} : floatx2{hi[2 * j - 4], hi[2 * j - 3]};
-    const bf16x2 hp = __builtin_convertvector(x, bf16x2);
-    const floatx2 r1 = x - __builtin_convertvector(hp, floatx2);
-    const bf16x2 mp = __builtin_convertvector(r1, bf16x2);
-    const bf16x2 lp = __builtin_convertvector(r1 - __builtin_convertvector(mp, floatx2), bf16x2);
+  for (int j = 0; j < 4; ++j) {
+    bf2 hp, mp, lp;
+    split_pair(j < 2 ? f2{lo[2 * j], lo[2 * j + 1]} : f2{hi[2 * j - 4], hi[2 * j - 3]}, hp, mp, lp);
     h[2 * j] = hp[0];
     h[2 * j + 1] = hp[1];
     m[2 * j] = mp[0];
@@ -885,18 +865,6 @@ __device__ __forceinline__ void split3(const floatx4& lo, const floatx4& hi, bf1
     l[2 * j] = lp[0];
     l[2 * j + 1] = lp[1];
   }
-}
-
-// c + A·B from the split operands: the six products down to 2^-16 |a||b|, smallest first
-__device__ __forceinline__ floatx4 mfma6(const bf16x8& ah, const bf16x8& am, const bf16x8& al,
-                                         const bf16x8& bh, const bf16x8& bm, const bf16x8& bl,
-                                         floatx4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
 }
 
 constexpr int kTrainAtop = 512;                       // A_top (compact row, zero padding)
@@ -925,7 +893,7 @@ struct TrainArgs {
 //   Z       the chunk's k-step of Z = X·Xᵀ (three 16x16 blocks, mfma6);
 //   loads   X(b+1)'s chunk s is issued into the registers just freed, so every chunk's loads
 //           have a whole example of latency cover (no second register set);
-//   image   the six bf16x8 parts go to a 6 KB per-wave LDS image [part][32 rows][32 columns]
+//   image   the six bf8 parts go to a 6 KB per-wave LDS image [part][32 rows][32 columns]
 //           (chunk-swizzled, ch_off: conflict-free writes and transposed reads), read back
 //           column-major with ds_read_b64_tr_b16 as the A operand of
 //   Uᵀ      Uᵀ = Xᵀ·(M + Mᵀ) for the chunk's two 16-column tiles: the MFMA result puts four
@@ -945,9 +913,9 @@ typedef __attribute__((address_space(3))) shortx4 lds_shortx4;
 
 // the Uᵀ product: c + Xᵀ·S from the split operands, the six products smallest first
 // (X as A, S as B: m·m, l·h, h·l, m·h, h·m, h·h)
-__device__ __forceinline__ floatx4 mfma6_xs(const bf16x8& xh, const bf16x8& xm, const bf16x8& xl,
-                                            const bf16x8& sh, const bf16x8& sm, const bf16x8& sl,
-                                            floatx4 c) {
+__device__ __forceinline__ f4 mfma6_xs(const bf8& xh, const bf8& xm, const bf8& xl,
+                                            const bf8& sh, const bf8& sm, const bf8& sl,
+                                            f4 c) {
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xm, sm, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl, sh, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, sl, c, 0, 0, 0);
@@ -986,7 +954,7 @@ __global__ __launch_bounds__(256, 2) void dlrm_train_chunk(GatherSrc src, int64_
   __shared__ __attribute__((aligned(16))) float qlane[64][12];
   __shared__ __attribute__((aligned(16))) float qsh[kTrainAtop];
   // S's split parts (the Uᵀ product's B operands), read per chunk: 24 VGPRs the loop needs more
-  __shared__ __attribute__((aligned(16))) bf16x8 sash[2][3][64];
+  __shared__ __attribute__((aligned(16))) bf8 sash[2][3][64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t first = ((int64_t)blockIdx.x * 4 + wave) * epw;
   const int64_t last = first + epw < batch ? first + epw : batch;
@@ -1027,7 +995,7 @@ __global__ __launch_bounds__(256, 2) void dlrm_train_chunk(GatherSrc src, int64_
   if (wave == 1) {
 #pragma unroll
     for (int ib = 0; ib < 2; ++ib) {
-      floatx4 v[2];
+      f4 v[2];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int m = 16 * ib + r, kk = 8 * g + j;
@@ -1072,8 +1040,8 @@ __global__ __launch_bounds__(256, 2) void dlrm_train_chunk(GatherSrc src, int64_
     if (lane < S) return id_ok ? src.table + (lo + id) * D : kZeroRow;
     return (lane == S && live) ? src.dense + (b < last ? b : first) * D : kZeroRow;
   };
-  floatx4 a0[NT], a1[NT];
-  floatx4 dn4;
+  f4 a0[NT], a1[NT];
+  f4 dn4;
   const float* p0 = nullptr;
   const float* p1 = nullptr;
   auto load_chunk = [&](int s) {
@@ -1108,7 +1076,7 @@ __global__ __launch_bounds__(256, 2) void dlrm_train_chunk(GatherSrc src, int64_
         p1 = shfl_ptr(nxt, 16 + r);
       }
       id_next = raw_id(b + 2);
-      const floatx4 dn = dn4;
+      const f4 dn = dn4;
       float xb[kTrainNI];
       // x_b (13 inputs) and label_b are wave-uniform: scalar loads, counted by lgkmcnt, so
       // reading them waits on nothing in the vector memory queue (a vector load + readlane
@@ -1121,18 +1089,18 @@ __global__ __launch_bounds__(256, 2) void dlrm_train_chunk(GatherSrc src, int64_
       const float lb = ((const cfloat*)ta.label)[bq];
       load_side(b + 1);
       float* de = ta.grad_emb + b * S * (int64_t)D;
-      floatx4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = c00, c11 = c00;
+      f4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = c00, c11 = c00;
       // transposed-read addresses (lane 4q + p of group g: row 8g + 4h + q, columns 4p.. of
       // 16-column tile tt, through ch_off's swizzle)
       const int q = (lanev >> 2) & 3, p4 = lanev & 3;
 #pragma unroll
       for (int s = 0; s < NC; ++s) {
-        bf16x8 sa[2][3];
+        bf8 sa[2][3];
 #pragma unroll
         for (int ib = 0; ib < 2; ++ib)
 #pragma unroll
           for (int pt = 0; pt < 3; ++pt) sa[ib][pt] = sash[ib][pt][lanev & 63];
-        bf16x8 h0, m0, l0, h1, m1, l1;
+        bf8 h0, m0, l0, h1, m1, l1;
         split3(a0[2 * s], a0[2 * s + 1], h0, m0, l0);
         split3(a1[2 * s], a1[2 * s + 1], h1, m1, l1);
         __builtin_amdgcn_sched_barrier(0);
@@ -1142,16 +1110,16 @@ __global__ __launch_bounds__(256, 2) void dlrm_train_chunk(GatherSrc src, int64_
         c01 = mfma6(h0, m0, l0, h1, m1, l1, c01);
         c11 = mfma6(h1, m1, l1, h1, m1, l1, c11);
         // the parts → the chunk image (rows r and 16 + r, columns 8g .. 8g + 7)
-        *reinterpret_cast<bf16x8*>(img + 0 * kChPlane + ch_off(r, 8 * g)) = h0;
-        *reinterpret_cast<bf16x8*>(img + 1 * kChPlane + ch_off(r, 8 * g)) = m0;
-        *reinterpret_cast<bf16x8*>(img + 2 * kChPlane + ch_off(r, 8 * g)) = l0;
-        *reinterpret_cast<bf16x8*>(img + 0 * kChPlane + ch_off(16 + r, 8 * g)) = h1;
-        *reinterpret_cast<bf16x8*>(img + 1 * kChPlane + ch_off(16 + r, 8 * g)) = m1;
-        *reinterpret_cast<bf16x8*>(img + 2 * kChPlane + ch_off(16 + r, 8 * g)) = l1;
+        *reinterpret_cast<bf8*>(img + 0 * kChPlane + ch_off(r, 8 * g)) = h0;
+        *reinterpret_cast<bf8*>(img + 1 * kChPlane + ch_off(r, 8 * g)) = m0;
+        *reinterpret_cast<bf8*>(img + 2 * kChPlane + ch_off(r, 8 * g)) = l0;
+        *reinterpret_cast<bf8*>(img + 0 * kChPlane + ch_off(16 + r, 8 * g)) = h1;
+        *reinterpret_cast<bf8*>(img + 1 * kChPlane + ch_off(16 + r, 8 * g)) = m1;
+        *reinterpret_cast<bf8*>(img + 2 * kChPlane + ch_off(16 + r, 8 * g)) = l1;
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
-          bf16x8 xp[3];
+          bf8 xp[3];
 #pragma unroll
           for (int pt = 0; pt < 3; ++pt) {
             const int o0 = pt * kChPlane + ch_off(8 * g + q, 16 * tt + 4 * p4);
@@ -1161,18 +1129,18 @@ __global__ __launch_bounds__(256, 2) void dlrm_train_chunk(GatherSrc src, int64_
             const shortx4 hi4 =
                 __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_shortx4*)(img + o1));
             const shortx8 v8 = __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
-            xp[pt] = __builtin_bit_cast(bf16x8, v8);
+            xp[pt] = __builtin_bit_cast(bf8, v8);
           }
-          floatx4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
+          f4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
           d0 = mfma6_xs(xp[0], xp[1], xp[2], sa[0][0], sa[0][1], sa[0][2], d0);
           d1 = mfma6_xs(xp[0], xp[1], xp[2], sa[1][0], sa[1][1], sa[1][2], d1);
           // lane (r, g): U[16 ib + r][32 s + 16 tt + 4g ..+3] → the staging rows (and U's row S,
           // the bottom-MLP row, to ubot)
           const int col = 16 * tt + 4 * g;
-          *reinterpret_cast<floatx4*>(stg + r * kChStageLd + col) = d0;
-          *reinterpret_cast<floatx4*>(stg + (16 + r) * kChStageLd + col) = d1;
-          if (r == S) *reinterpret_cast<floatx4*>(ubot + 32 * s + col) = d0;
-          if (16 + r == S) *reinterpret_cast<floatx4*>(ubot + 32 * s + col) = d1;
+          *reinterpret_cast<f4*>(stg + r * kChStageLd + col) = d0;
+          *reinterpret_cast<f4*>(stg + (16 + r) * kChStageLd + col) = d1;
+          if (r == S) *reinterpret_cast<f4*>(ubot + 32 * s + col) = d0;
+          if (16 + r == S) *reinterpret_cast<f4*>(ubot + 32 * s + col) = d1;
         }
         __builtin_amdgcn_wave_barrier();
         // the chunk's 128-B row segments to HBM: 8 rows per store, 8 lanes per row (a 64-B
@@ -1180,9 +1148,9 @@ __global__ __launch_bounds__(256, 2) void dlrm_train_chunk(GatherSrc src, int64_
 #pragma unroll
         for (int pp = 0; pp < 4; ++pp) {
           const int i = 8 * pp + (lanev >> 3), c8 = lanev & 7;
-          const floatx4 v = *reinterpret_cast<const floatx4*>(stg + i * kChStageLd + 4 * c8);
+          const f4 v = *reinterpret_cast<const f4*>(stg + i * kChStageLd + 4 * c8);
           if (i < S)
-            __builtin_nontemporal_store(v, reinterpret_cast<floatx4*>(de + i * D + 32 * s + 4 * c8));
+            __builtin_nontemporal_store(v, reinterpret_cast<f4*>(de + i * D + 32 * s + 4 * c8));
         }
         __builtin_amdgcn_wave_barrier();  // the next chunk's image / staging writes follow
       }
@@ -1197,21 +1165,20 @@ __global__ __launch_bounds__(256, 2) void dlrm_train_chunk(GatherSrc src, int64_
       }
       float hacc = 0.f;
       {
-        const floatx4* ql = reinterpret_cast<const floatx4*>(&qlane[lanev & 63][0]);
+        const f4* ql = reinterpret_cast<const f4*>(&qlane[lanev & 63][0]);
 #pragma unroll
         for (int q4 = 0; q4 < 3; ++q4) {
-          const floatx4 qv = ql[q4];
+          const f4 qv = ql[q4];
 #pragma unroll
           for (int k = 0; k < 4; ++k) hacc += zr[4 * q4 + k] * qv[k];
         }
-        const floatx4 qd = *reinterpret_cast<const floatx4*>(&qsh[nzc + 4 * cl]);
+        const f4 qd = *reinterpret_cast<const f4*>(&qsh[nzc + 4 * cl]);
         if (rg == 0) {
 #pragma unroll
           for (int k = 0; k < 4; ++k) hacc += dn[k] * qd[k];
         }
       }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) hacc += __shfl_xor(hacc, off);
+      hacc = wave_sum(hacc);
       const float p = 1.f / (1.f + expf(-(hacc + cc)));
       {
         const float pc = fminf(fmaxf(p, ta.eps), 1.f - ta.eps);
@@ -1232,8 +1199,8 @@ __global__ __launch_bounds__(256, 2) void dlrm_train_chunk(GatherSrc src, int64_
 #pragma unroll
       for (int k = 0; k < 4; ++k) ad[k] += dn[k] * G;
       {  // the bottom-MLP row from U's row S
-        const floatx4 v = *reinterpret_cast<const floatx4*>(ubot + 4 * cl);
-        const floatx4 qdn = *reinterpret_cast<const floatx4*>(&qsh[nzc + 4 * cl]);
+        const f4 v = *reinterpret_cast<const f4*>(ubot + 4 * cl);
+        const f4 qdn = *reinterpret_cast<const f4*>(&qsh[nzc + 4 * cl]);
 #pragma unroll
         for (int k = 0; k < DPL; ++k) {
           const int c = DPL * rg + k;

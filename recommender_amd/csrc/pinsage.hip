@@ -25,14 +25,6 @@
 
 namespace rs {
 
-int32_t radix_sort_pairs(uint32_t* keys_in, int32_t* vals_in, uint32_t* keys_out,
-                         int32_t* vals_out, int64_t n, int64_t n_rows, void* ws, size_t ws_bytes,
-                         hipStream_t st);
-size_t radix_sort_ws_size(int64_t n);
-int32_t exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, int32_t* total, void* ws,
-                           size_t ws_bytes, hipStream_t st);
-size_t exclusive_scan_ws_size(int64_t n);
-
 struct Graph {
   const int64_t* i2u_ptr;
   const int32_t* i2u;
@@ -863,12 +855,19 @@ extern "C" int32_t rs_metapath_walk(const int64_t* i2u_indptr, const int32_t* i2
   return RS_OK;
 }
 
+// the workspace layouts below are braced lists: the takes run in the order written
+struct ItemPairsWs {
+  int32_t *tmp, *flag, *offs;
+  void* sws;
+};
+static ItemPairsWs item_pairs_ws(Carver& c, int32_t batch) {
+  return {c.take<int32_t>((size_t)3 * batch), c.take<int32_t>(batch), c.take<int32_t>(batch),
+          c.take<char>(exclusive_scan_ws_size(batch))};
+}
+
 extern "C" size_t rs_item_pairs_workspace_size(int32_t batch) {
   Carver c(nullptr, 0);
-  c.take<int32_t>((size_t)3 * batch);
-  c.take<int32_t>(batch);
-  c.take<int32_t>(batch);
-  c.take<char>(exclusive_scan_ws_size(batch));
+  item_pairs_ws(c, batch);
   return c.off + 256;
 }
 
@@ -886,10 +885,7 @@ static int32_t item_pairs(const int64_t* i2u_indptr, const int32_t* i2u_idx,
     return RS_OK;
   }
   Carver c(workspace, ws_bytes);
-  int32_t* tmp = c.take<int32_t>((size_t)3 * batch);
-  int32_t* flag = c.take<int32_t>(batch);
-  int32_t* offs = c.take<int32_t>(batch);
-  void* sws = c.take<char>(exclusive_scan_ws_size(batch));
+  const auto [tmp, flag, offs, sws] = item_pairs_ws(c, batch);
   if (!c.ok()) {
     set_error("rs_item_pairs: workspace too small (%zu > %zu)", c.off, ws_bytes);
     return RS_E_WORKSPACE;
@@ -996,12 +992,18 @@ extern "C" int32_t rs_pinsage_neighbors_at(const int64_t* i2u_indptr, const int3
                            excl_table, excl_capacity, nbr, cnt, stream);
 }
 
+struct UniqueFirstWs {
+  int32_t *mark, *flag, *pos;
+  void* sws;
+};
+static UniqueFirstWs unique_first_ws(Carver& c, int64_t n_nodes, int64_t n) {
+  return {c.take<int32_t>(n_nodes), c.take<int32_t>(n), c.take<int32_t>(n),
+          c.take<char>(exclusive_scan_ws_size(n))};
+}
+
 extern "C" size_t rs_unique_first_workspace_size(int64_t n_nodes, int64_t n) {
   Carver c(nullptr, 0);
-  c.take<int32_t>(n_nodes);
-  c.take<int32_t>(n);
-  c.take<int32_t>(n);
-  c.take<char>(exclusive_scan_ws_size(n));
+  unique_first_ws(c, n_nodes, n);
   return c.off + 256;
 }
 
@@ -1017,10 +1019,7 @@ extern "C" int32_t rs_unique_first(const int32_t* ids, int64_t n, int64_t n_node
     return RS_OK;
   }
   Carver c(workspace, ws_bytes);
-  int32_t* mark = c.take<int32_t>(n_nodes);
-  int32_t* flag = c.take<int32_t>(n);
-  int32_t* pos = c.take<int32_t>(n);
-  void* sws = c.take<char>(exclusive_scan_ws_size(n));
+  const auto [mark, flag, pos, sws] = unique_first_ws(c, n_nodes, n);
   if (!c.ok()) {
     set_error("rs_unique_first: workspace too small (%zu > %zu)", c.off, ws_bytes);
     return RS_E_WORKSPACE;
@@ -1038,17 +1037,22 @@ extern "C" int32_t rs_unique_first(const int32_t* ids, int64_t n, int64_t n_node
   return RS_OK;
 }
 
+struct BlockWs {
+  int32_t *valid, *epos, *total;
+  uint32_t* keys;
+  int32_t* vals;
+  uint32_t* skeys;  // sorted keys
+  void *sws, *rws;
+};
+static BlockWs block_ws(Carver& c, int64_t cap) {
+  return {c.take<int32_t>(cap),  c.take<int32_t>(cap),  c.take<int32_t>(1),
+          c.take<uint32_t>(cap), c.take<int32_t>(cap),  c.take<uint32_t>(cap),
+          c.take<char>(exclusive_scan_ws_size(cap)), c.take<char>(radix_sort_ws_size(cap))};
+}
+
 extern "C" size_t rs_pinsage_block_workspace_size(int64_t n_dst, int32_t k) {
-  const int64_t cap = n_dst * k;
   Carver c(nullptr, 0);
-  c.take<int32_t>(cap);             // valid
-  c.take<int32_t>(cap);             // epos
-  c.take<int32_t>(1);               // total
-  c.take<uint32_t>(cap);            // keys
-  c.take<int32_t>(cap);             // vals
-  c.take<uint32_t>(cap);            // sorted keys
-  c.take<char>(exclusive_scan_ws_size(cap));
-  c.take<char>(radix_sort_ws_size(cap));
+  block_ws(c, n_dst * k);
   return c.off + 256;
 }
 
@@ -1068,14 +1072,7 @@ extern "C" int32_t rs_pinsage_block(const int32_t* nbr_local, const int32_t* cnt
     return RS_OK;
   }
   Carver c(workspace, ws_bytes);
-  int32_t* valid = c.take<int32_t>(cap);
-  int32_t* epos = c.take<int32_t>(cap);
-  int32_t* total = c.take<int32_t>(1);
-  uint32_t* keys = c.take<uint32_t>(cap);
-  int32_t* vals = c.take<int32_t>(cap);
-  uint32_t* skeys = c.take<uint32_t>(cap);
-  void* sws = c.take<char>(exclusive_scan_ws_size(cap));
-  void* rws = c.take<char>(radix_sort_ws_size(cap));
+  const auto [valid, epos, total, keys, vals, skeys, sws, rws] = block_ws(c, cap);
   if (!c.ok()) {
     set_error("rs_pinsage_block: workspace too small (%zu > %zu)", c.off, ws_bytes);
     return RS_E_WORKSPACE;

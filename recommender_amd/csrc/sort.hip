@@ -475,10 +475,6 @@ static SortPlan plan_sort(int64_t n_ids, int64_t n_rows) {
   return p;
 }
 
-int32_t exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, int32_t* total, void* ws,
-                           size_t ws_bytes, hipStream_t st);
-size_t exclusive_scan_ws_size(int64_t n);
-
 // workspace: keys_alt[n], vals_alt[n], hist[BINS * n_tiles], digit totals[BINS]
 static size_t sort_ws_layout(int64_t n_ids, Carver& c, uint32_t** keys_alt, int32_t** vals_alt,
                              int32_t** hist, int32_t** totals) {
@@ -1477,7 +1473,7 @@ __global__ __launch_bounds__(256) void runs_merge_kernel(const int32_t* __restri
     rows_out[out] = kout;
     pos_out[out] = (int32_t)e;
   }
-  if (__any(oob) && (threadIdx.x & 63) == 0) flag_oob(err_flag);
+  flag_oob_wave(oob, err_flag);
 }
 
 static bool small_eligible(int64_t n_ids, int n_slots, int world, int64_t n_rows) {
@@ -1588,10 +1584,19 @@ static int32_t sort_ids_impl(const void* ids, int32_t id_dtype, int64_t n_ids,
                              int32_t* n_unique, int32_t* err_flag, void* workspace, size_t ws_bytes,
                              hipStream_t st, const uint8_t* valid, int64_t max_slot_rows);
 
+// head of the LSD form's workspace: the (key, position) pairs pass 0 makes; the radix sort's own
+// workspace follows (the layouts here are braced lists: the takes run in the order written)
+struct LsdPairs {
+  uint32_t* keys;
+  int32_t* vals;
+};
+static LsdPairs lsd_pairs(Carver& c, int64_t n_ids) {
+  return {c.take<uint32_t>(n_ids), c.take<int32_t>(n_ids)};
+}
+
 extern "C" size_t rs_sort_ids_workspace_size(int64_t n_ids) {
   Carver c(nullptr, 0);
-  c.take<uint32_t>(n_ids);
-  c.take<int32_t>(n_ids);
+  lsd_pairs(c, n_ids);
   const size_t lsd = c.off + radix_sort_ws_size(n_ids) + exclusive_scan_ws_size(n_ids) + 1024;
   const size_t seg = seg_ws_size(n_ids);
   return lsd > seg ? lsd : seg;
@@ -1639,10 +1644,17 @@ extern "C" int32_t rs_sort_ids_sharded(const void* ids, int32_t id_dtype, int64_
                        n_rows);
 }
 
+struct UniqueWs {
+  int32_t* excl;
+  void* scan_ws;
+};
+static UniqueWs unique_ws(Carver& c, int64_t n_ids) {
+  return {c.take<int32_t>(n_ids), c.take<char>(exclusive_scan_ws_size(n_ids))};
+}
+
 extern "C" size_t rs_unique_inverse_workspace_size(int64_t n_ids) {
   Carver c(nullptr, 0);
-  c.take<int32_t>(n_ids > 0 ? n_ids : 1);
-  c.take<char>(exclusive_scan_ws_size(n_ids > 0 ? n_ids : 1));
+  unique_ws(c, n_ids > 0 ? n_ids : 1);
   return c.off + 256;
 }
 
@@ -1664,8 +1676,7 @@ extern "C" int32_t rs_unique_inverse(const uint32_t* sorted_keys, const int32_t*
     return RS_OK;
   }
   Carver c(workspace, ws_bytes);
-  int32_t* excl = c.take<int32_t>(n_ids);
-  void* scan_ws = c.take<char>(exclusive_scan_ws_size(n_ids));
+  const auto [excl, scan_ws] = unique_ws(c, n_ids);
   if (!c.ok()) {
     set_error("unique workspace too small");
     return RS_E_WORKSPACE;
@@ -1719,8 +1730,7 @@ static int32_t sort_ids_impl(const void* ids, int32_t id_dtype, int64_t n_ids,
     return RS_OK;
   }
   Carver c(workspace, ws_bytes);
-  uint32_t* keys = c.take<uint32_t>(n_ids);
-  int32_t* vals = c.take<int32_t>(n_ids);
+  const auto [keys, vals] = lsd_pairs(c, n_ids);
   size_t rest_off = align_up(c.off, 256);
   if (rest_off > ws_bytes) {
     set_error("sort workspace too small");

@@ -22,19 +22,23 @@ struct SortedScratch {
   size_t rest_bytes;
 };
 
-size_t sorted_head(int64_t n) {
-  rs::Carver c(nullptr, 0);
-  c.take<uint32_t>(n);
-  c.take<int32_t>(n);
+// the sorted (row, position) pairs at the head of the workspace; returns the bytes they take
+size_t take_sorted(rs::Carver& c, int64_t n, SortedScratch& s) {
+  s.rows = c.take<uint32_t>(n);
+  s.pos = c.take<int32_t>(n);
   return rs::align_up(c.off, 256);
 }
 
+size_t sorted_head(int64_t n) {
+  rs::Carver c(nullptr, 0);
+  SortedScratch s;
+  return take_sorted(c, n, s);
+}
+
 bool carve(void* ws, size_t bytes, int64_t n, SortedScratch& s) {
-  const size_t head = sorted_head(n);
-  if (!ws || bytes < head) return false;
   rs::Carver c(ws, bytes);
-  s.rows = c.take<uint32_t>(n);
-  s.pos = c.take<int32_t>(n);
+  const size_t head = take_sorted(c, n, s);
+  if (!ws || bytes < head) return false;
   s.rest = static_cast<char*>(ws) + head;
   s.rest_bytes = bytes - head;
   return true;

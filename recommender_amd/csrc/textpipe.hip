@@ -23,10 +23,6 @@
 
 namespace rs {
 
-int32_t exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, int32_t* total, void* ws,
-                           size_t ws_bytes, hipStream_t st);
-size_t exclusive_scan_ws_size(int64_t n);
-
 namespace {
 
 constexpr int kMaxCols = 32;
@@ -562,10 +558,18 @@ extern "C" int32_t rs_map_insert(const uint64_t* key_hash, int64_t n, uint64_t* 
   return RS_OK;
 }
 
+// the two workspace layouts are braced lists: the takes run in the order written
+struct JoinWs {
+  int32_t* offs;
+  void* sws;
+};
+static JoinWs join_ws(Carver& c, int64_t n_lines) {
+  return {c.take<int32_t>(n_lines), c.take<char>(exclusive_scan_ws_size(n_lines))};
+}
+
 extern "C" size_t rs_aliccp_join_workspace_size(int64_t n_lines) {
   Carver c(nullptr, 0);
-  c.take<int32_t>(n_lines);
-  c.take<char>(exclusive_scan_ws_size(n_lines));
+  join_ws(c, n_lines);
   return c.off + 256;
 }
 
@@ -587,8 +591,7 @@ extern "C" int32_t rs_aliccp_join(const int32_t* keep, int64_t n_lines, int32_t 
     return RS_OK;
   }
   Carver c(workspace, ws_bytes);
-  int32_t* offs = c.take<int32_t>(n_lines);
-  void* sws = c.take<char>(exclusive_scan_ws_size(n_lines));
+  const auto [offs, sws] = join_ws(c, n_lines);
   if (!c.ok()) {
     set_error("rs_aliccp_join: workspace too small");
     return RS_E_WORKSPACE;
@@ -652,10 +655,17 @@ extern "C" int32_t rs_dien_parse(const uint8_t* text, int64_t n_bytes, const int
   return RS_OK;
 }
 
+struct ItemCatWs {
+  unsigned long long* last;
+  uint64_t* slot_cat;
+};
+static ItemCatWs item_cat_ws(Carver& c, int64_t item_capacity) {
+  return {c.take<unsigned long long>(item_capacity), c.take<uint64_t>(item_capacity)};
+}
+
 extern "C" size_t rs_dien_item_cat_workspace_size(int64_t item_capacity) {
   Carver c(nullptr, 0);
-  c.take<unsigned long long>(item_capacity);
-  c.take<uint64_t>(item_capacity);
+  item_cat_ws(c, item_capacity);
   return c.off + 256;
 }
 
@@ -672,8 +682,7 @@ extern "C" int32_t rs_dien_item_cat(const uint64_t* item_hash, const uint64_t* c
                "rs_dien_item_cat: bad arguments");
   hipStream_t st = as_stream(stream);
   Carver c(workspace, ws_bytes);
-  unsigned long long* last = c.take<unsigned long long>(item_capacity);
-  uint64_t* slot_cat = c.take<uint64_t>(item_capacity);
+  const auto [last, slot_cat] = item_cat_ws(c, item_capacity);
   if (!c.ok()) {
     set_error("rs_dien_item_cat: workspace too small");
     return RS_E_WORKSPACE;

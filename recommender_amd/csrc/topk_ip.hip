@@ -33,8 +33,6 @@
 namespace rs {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 constexpr int kTileQ = 32;                  // queries per block (MFMA rows)
 constexpr int kTileI = 32;                  // items per wave tile (MFMA columns)
 constexpr int kIpWaves = 4;
@@ -417,27 +415,13 @@ size_t ip_lds_bytes(int32_t dim, int W) {
                           (size_t)kTileQ * kCap * 2 + (size_t)kTileQ * 4);
 }
 
-int cu_count() {
-  static const int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0) {
-      (void)hipGetLastError();
-      return 256;
-    }
-    return cus;
-  }();
-  return n;
-}
-
 // the item ranges of a call: the forced count, or enough blocks for two per CU with ranges of
 // at least 1024 items
 int64_t pick_splits(int32_t n_queries, int64_t n_items, int32_t n_splits) {
   if (n_splits > 0) return n_splits;
   if (n_queries <= 0 || n_items <= 0) return 1;
   const int64_t q_tiles = ceil_div(n_queries, kTileQ);
-  int64_t s = ceil_div(2 * (int64_t)cu_count(), q_tiles);
+  int64_t s = ceil_div(2 * (int64_t)device_cus(), q_tiles);
   s = s < n_items / 1024 ? s : n_items / 1024;
   s = s < kAutoSplitMax ? s : kAutoSplitMax;
   return s < 1 ? 1 : s;
