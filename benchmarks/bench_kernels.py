@@ -606,6 +606,111 @@ def embedding_q8(iters, out, rounds=5):
         torch.cuda.empty_cache()
 
 
+def dlrm_score(iters, out, rounds=5):
+    """DLRM scoring for serving against the parent's fastest forward, interleaved in one process
+    (`rounds` rounds of every variant, each timed over `iters` launches; medians reported, every
+    round's time next to them). One table of 8M rows (fp32 4 GB at D = 128: past the Infinity
+    Cache), 26 slots laid out as slab offsets over it, B = 65 536, int32 ids, uniform and the
+    bench's Zipf(1.05) per slot, D = 128 and 64. Bytes per example, S = 26, nz = 351:
+      rs_dlrm_interaction_fwd_head (D = 128 only)  read S·4D + 4D + 4S, written 4(nz + D) + 4
+      rs_dlrm_score                                 read S·4D + 4D + 4S, written 4
+      rs_dlrm_score_q8 (16-byte and 4-byte reads)   read S·q_ld + 4D + 4S, written 4
+    The 4-byte read form is reached by the same table placed 4 bytes off its allocation. Module
+    level (uniform ids): DLRM.forward under no_grad (the parent's route: interaction row to HBM,
+    top MLP as three GEMMs) against DLRM.score and against the quantised model's forward; their
+    bytes are the kernel's above (the MLPs' weights are not counted)."""
+    from recommender_amd.ctr.train import build_model
+    from recommender_amd.quantized import QuantizedEmbedding
+    from recommender_amd.synthetic import _spread, bounded_zipf
+
+    rng = np.random.default_rng(4)
+    dev = torch.device(DEV, 0)
+    st = L.stream_ptr(dev)
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    S, B = 26, 65536
+    card = 8_000_000 // S
+    V = card * S
+    so = torch.arange(S + 1, dtype=torch.int64, device=DEV) * card
+    id_sets = {"uniform": rng.integers(0, card, (B, S)).astype(np.int32),
+               "zipf1.05": _spread(bounded_zipf(rng, B * S, card), card).astype(np.int32)
+               .reshape(B, S)}
+    nz = S * (S + 1) // 2
+    for D in (128, 64):
+        g = torch.Generator(device=DEV)
+        g.manual_seed(4)
+        model = build_model("DLRM", D, V, S, 13, dev, slot_cardinalities=[card] * S, generator=g)
+        table = model.embedding_layer.weight.detach()
+        q_ld = int(L.lib().rs_q8_row_bytes(D))
+        bufs = [torch.zeros(V * q_ld + 16, dtype=torch.uint8, device=DEV) for _ in range(2)]
+        qts = [b[sh:sh + V * q_ld].view(V, q_ld) for b, sh in zip(bufs, (0, 4))]
+        for qt in qts:
+            L.call("rs_quantize_rows_q8", L.ptr(table), D, V, D, L.ptr(qt), q_ld, L.ptr(err), st)
+        width = (nz + D + 15) // 16 * 16
+        q = torch.randn(width, device=DEV) * 0.05
+        c = torch.full((1,), 0.1, device=DEV)
+        dense = torch.relu(torch.randn(B, D, device=DEV))
+        row = torch.empty(B, width, device=DEV)
+        y = torch.empty(B, device=DEV)
+        qmodel = build_model("DLRM", D, S, S, 13, dev, slot_cardinalities=[1] * S)
+        qmodel.bottom_mlp, qmodel.top_mlp = model.bottom_mlp, model.top_mlp
+        qmodel.embedding_layer = QuantizedEmbedding(V, D, device=dev, slot_offsets=so, q_ld=q_ld,
+                                                    qweight=qts[0])
+        rd = S * 4 * D + 4 * D + 4 * S
+        rq = S * q_ld + 4 * D + 4 * S
+        for dist, ids_np in id_sets.items():
+            ids = torch.from_numpy(ids_np).to(DEV)
+            x = {"cat_features": ids, "int_features": torch.rand(B, 13, device=DEV)}
+
+            def head():
+                L.call("rs_dlrm_interaction_fwd_head", L.ptr(table), V, D, L.ptr(ids), 0, S,
+                       L.ptr(so), L.ptr(dense), B, L.ptr(row), width, L.ptr(q), L.ptr(c), 2,
+                       L.ptr(y), L.ptr(err), st)
+
+            def score():
+                L.call("rs_dlrm_score", L.ptr(table), V, D, L.ptr(ids), 0, S, L.ptr(so),
+                       L.ptr(dense), B, L.ptr(q), L.ptr(c), 2, L.ptr(y), L.ptr(err), st)
+
+            def score_q8(qt):
+                L.call("rs_dlrm_score_q8", L.ptr(qt), q_ld, V, D, L.ptr(ids), 0, S, L.ptr(so),
+                       L.ptr(dense), B, L.ptr(q), L.ptr(c), 2, L.ptr(y), L.ptr(err), st)
+
+            def no_grad(m, fn):
+                def run():
+                    with torch.no_grad():
+                        fn(m)
+                return run
+
+            variants = []
+            if D == 128:
+                variants.append(("rs_dlrm_interaction_fwd_head fp32", head,
+                                 B * (rd + 4 * (nz + D) + 4)))
+            variants += [("rs_dlrm_score fp32", score, B * (rd + 4)),
+                         ("rs_dlrm_score_q8 16-byte reads", lambda: score_q8(qts[0]), B * (rq + 4)),
+                         ("rs_dlrm_score_q8 4-byte reads", lambda: score_q8(qts[1]), B * (rq + 4))]
+            if dist == "uniform":
+                variants += [
+                    ("DLRM.forward no_grad fp32", no_grad(model, lambda m: m(x)),
+                     B * (rd + 4 * (nz + D) + 4)),
+                    ("DLRM.score fp32", no_grad(model, lambda m: m.score(x)), B * (rd + 4)),
+                    ("DLRM.forward quantised", no_grad(qmodel, lambda m: m(x)), B * (rq + 4))]
+            times = {v[0]: [] for v in variants}
+            for _ in range(rounds):
+                for name, fn, _ in variants:
+                    times[name].append(timed(fn, iters))
+            med = {k: float(np.median(v)) for k, v in times.items()}
+            base = "rs_dlrm_interaction_fwd_head fp32" if D == 128 else "rs_dlrm_score fp32"
+            for name, _, nbytes in variants:
+                cfg = {"rows": V, "D": D, "q_ld": q_ld, "slots": S, "batch": B, "ids": dist,
+                       "rounds_us": [round(t, 1) for t in times[name]]}
+                ref = "DLRM.forward no_grad fp32" if name.startswith("DLRM.") else base
+                cfg[f"time_of_{ref.split()[0]}_over_this"] = round(med[ref] / med[name], 3)
+                report(f"dlrm_score {name} (interleaved, median of {rounds})", cfg, med[name],
+                       nbytes, out)
+        assert int(err.item()) == 0
+        del model, qmodel, table, qts, bufs, row
+        torch.cuda.empty_cache()
+
+
 def criteo(iters, out):
     """Criteo TSV ingestion: line index + parse + vocab lookup over a ~45 MB synthetic text
     (algorithmic bytes: text read once, outputs written once)."""

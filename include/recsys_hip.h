@@ -592,6 +592,52 @@ int32_t rs_dlrm_interaction_bwd_rank1(const float* table, int64_t n_rows, int32_
                                       int64_t width, float* grad_emb, float* grad_dense,
                                       void* stream);
 
+/* DLRM scoring for serving (ctr/model.py:49-57 without the row): ids in, one prediction per
+ * example out, rows read from an fp32 table (rs_dlrm_score) or an RS_Q8 one (rs_dlrm_score_q8,
+ * a-1c's row format). Forward only.
+ *
+ * Computes, per example b, with q [F(F-1)/2 + D], c [1] and act (0 linear, 1 relu, 2 sigmoid)
+ *   those of rs_dlrm_interaction_fwd_head (q, c from rs_chain3_vec_compose over the compact row):
+ *   X(b) = [ row(b,0), ..., row(b,S-1), dense[b] ]  (F = n_slots + 1 rows; row = the table row of
+ *   the slot's id, for RS_Q8 its dequantised elements),
+ *   z = the strict-upper pairs of X·Xᵀ in compact (row-major) order, nz = F(F-1)/2 of them,
+ *   y[b] = act(z·q[0..nz) + dense[b]·q[nz..nz+D) + c[0]).
+ *   Nothing but y[0..batch) and the error flag is written.
+ * Ids: an out-of-range id, negatives included, reads as a zero row and sets RS_ERRBIT_OOB in
+ *   err_flag (may be NULL). slot_offsets as rs_dlrm_interaction_fwd (NULL: one shared table).
+ * Shapes: F <= 32; D = 128 or D = 64.
+ * Arithmetic (fixed: results are bit-reproducible), that of rs_dlrm_interaction_fwd_head's
+ *   kernel: with r = lane % 16, g = lane / 16, three v_mfma_f32_16x16x4_f32 chains over rows r
+ *   and 16 + r, instruction (t, c) (t = 0..D/16-1 outer, c = 0..3 inner) taking columns
+ *   4g + 16t + c; then per lane the partial sum over compact positions o = lane + 64t in
+ *   ascending t, each term __fadd_rn(acc, __fmul_rn(z[o], q[o])) from acc = +0 — a rounded
+ *   multiply and a rounded add, never an fma (what rs_dlrm_interaction_fwd_head's kernel
+ *   compiles to under -ffp-contract=off; here written with the intrinsics, so it does not depend
+ *   on the compiler's contraction) — then the dense terms d = lane + 64t the same way, then the
+ *   __shfl_xor butterfly 32, 16, 8, 4, 2, 1 of __fadd_rn, then __fadd_rn(sum, c[0]), then
+ *   1.f / (1.f + expf(-v)), fmaxf(v, 0.f) or v. An RS_Q8 element is
+ *   __fadd_rn(__fmul_rn((float)code, scale), bias), never an fma.
+ * Contract: at D = 128 rs_dlrm_score equals rs_dlrm_interaction_fwd_head's y, bit for bit; at
+ *   D = 64 and D = 128 rs_dlrm_score_q8 equals rs_dlrm_score over the table
+ *   rs_dequantize_rows_q8 writes, bit for bit.
+ * Alignment chooses the access width, never the bits (a-1c's rule): the RS_Q8 table 4-byte
+ *   aligned, q_ld % 4 == 0, q_ld >= 8 + D; when the table and q_ld are multiples of 8 a row's
+ *   codes are read as 16-byte pieces, else as 4-byte ones. rs_dlrm_score needs the table, and
+ *   both need dense, 16-byte aligned (rs_dlrm_interaction_fwd_head's requirement).
+ * Errors: RS_E_INVALID for a null pointer with batch > 0 (err_flag and slot_offsets excepted),
+ *   batch < 0, a bad id dtype, a bad act, n_slots < 1, F > 32, a bad q_ld or alignment, and
+ *   n_rows <= 0 with batch > 0 (row 0 is what an absent row reads and discards);
+ *   RS_E_UNSUPPORTED for any other D; batch == 0 is a no-op. */
+int32_t rs_dlrm_score(const float* table, int64_t n_rows, int32_t D, const void* ids,
+                      int32_t id_dtype, int32_t n_slots, const int64_t* slot_offsets,
+                      const float* dense, int64_t batch, const float* q, const float* c,
+                      int32_t act, float* y, int32_t* err_flag, void* stream);
+int32_t rs_dlrm_score_q8(const uint8_t* qtable, int64_t q_ld, int64_t n_rows, int32_t D,
+                         const void* ids, int32_t id_dtype, int32_t n_slots,
+                         const int64_t* slot_offsets, const float* dense, int64_t batch,
+                         const float* q, const float* c, int32_t act, float* y,
+                         int32_t* err_flag, void* stream);
+
 /* a-5 DeepFM second-order term — ctr/model.py:21-23:
  *   out[b] = 0.5 * Σ_d ((Σ_f e[b,f,d])^2 - Σ_f e[b,f,d]^2). */
 int32_t rs_fm_fwd(const float* emb, int64_t batch, int32_t F, int32_t D, float* out, void* stream);

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "dlrm_shared.hpp"
 #include "row_io.hpp"
 
 namespace rs {
@@ -67,7 +68,7 @@ __device__ __forceinline__ void dequant_piece(const uint32_t (&w)[PW / 4], float
   for (int j = 0; j < PW / 4; ++j)
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      v[4 * j + k] = __fadd_rn(__fmul_rn((float)((w[j] >> (8 * k)) & 0xffu), scale), bias);
+      v[4 * j + k] = q8_value(w[j], k, scale, bias);
 }
 
 // the piece's columns [col0, col0 + PW) that lie in [0, dim), to row o; col0 is a multiple of 4

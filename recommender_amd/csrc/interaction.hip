@@ -22,6 +22,7 @@
 #include <tuple>
 #include <type_traits>
 
+#include "dlrm_shared.hpp"
 #include "mfma_x3.hpp"
 
 namespace rs {
@@ -34,13 +35,7 @@ struct InterMode {
 __device__ __forceinline__ bool keep_pair(int i, int j, int self_i) {
   return self_i ? (i >= j) : (i < j);
 }
-// compact output index of kept pair (i,j) (row-major boolean_mask order, ctr/layers.py:39-42)
-__device__ __forceinline__ int compact_index(int i, int j, int F, int self_i) {
-  return self_i ? (i * (i + 1) / 2 + j) : (i * F - i * (i + 1) / 2 + (j - i - 1));
-}
-__host__ __device__ inline int out_width(int F, int self_i, int skip_gather) {
-  return skip_gather ? F * F : (self_i ? F * (F + 1) / 2 : F * (F - 1) / 2);
-}
+// compact_index, out_width, compact_pair and shfl_ptr: dlrm_shared.hpp
 
 // X row source: embedding rows by id (DLRM) or a dense [B, F, D] tensor
 struct GatherSrc {
@@ -73,29 +68,6 @@ struct DenseSrc {
     return i < F ? x + (b * F + i) * (int64_t)D : nullptr;
   }
 };
-
-// invert compact_index for the non-self (i < j) layout: row i starts at i*F - i(i+1)/2
-__device__ __forceinline__ void compact_pair(int o, int F, int self_i, int& i, int& j) {
-  if (self_i) {  // o = i(i+1)/2 + j, j <= i
-    int ii = (int)((sqrtf(8.f * o + 1.f) - 1.f) * 0.5f);
-    while (ii * (ii + 1) / 2 > o) --ii;
-    while ((ii + 1) * (ii + 2) / 2 <= o) ++ii;
-    i = ii;
-    j = o - ii * (ii + 1) / 2;
-  } else {
-    const float b = 2.f * F - 1.f;
-    int ii = (int)((b - sqrtf(b * b - 8.f * o)) * 0.5f);
-    if (ii < 0) ii = 0;
-    while (ii > 0 && ii * F - ii * (ii + 1) / 2 > o) --ii;
-    while ((ii + 1) * F - (ii + 1) * (ii + 2) / 2 <= o) ++ii;
-    i = ii;
-    j = o - (ii * F - ii * (ii + 1) / 2) + ii + 1;
-  }
-}
-
-__device__ __forceinline__ const float* shfl_ptr(const float* p, int src) {
-  return reinterpret_cast<const float*>(__shfl(reinterpret_cast<long long>(p), src));
-}
 
 // ---------------------------------------------------------------------------------------
 // forward, MFMA: one wave per sample, 4 waves per block

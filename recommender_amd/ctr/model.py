@@ -4,7 +4,9 @@ Embedding(vocab_size, embedding_size) for all categorical slots (ctr/model.py:10
 DLRM's lookup → concat(bottom MLP) → DotInteraction(False, True) → concat chain
 (ctr/model.py:49-55) runs as ONE fused kernel pair (rs_dlrm_interaction_fwd/bwd): the rows are
 gathered by id straight into the MFMA interaction and the top-MLP input [Z, bottom] is written
-directly; `self.interaction` is kept for the reference attribute surface.
+directly; `self.interaction` is kept for the reference attribute surface. For serving,
+`DLRM.score` runs ctr/model.py:49-57 as one kernel that stores the prediction alone
+(rs_dlrm_score, or rs_dlrm_score_q8 over a quantised table).
 """
 from __future__ import annotations
 
@@ -12,7 +14,8 @@ import torch
 from torch import nn
 
 from ..embedding import Embedding, SlabEmbedding
-from ..functional import COMPACT_ALIGN, dlrm_interaction, dlrm_top, fm_interaction
+from ..functional import (COMPACT_ALIGN, dlrm_interaction, dlrm_score, dlrm_top,
+                          fm_interaction)
 from .layers import MLP, DotInteraction
 
 
@@ -93,7 +96,27 @@ class DLRM(nn.Module):
             return dlrm_interaction(view, inv, bmlp_activation, compact)
         return dlrm_interaction(self.embedding_layer, cat_features, bmlp_activation, compact)
 
+    def score(self, x):
+        """The prediction [B] for serving (ctr/model.py:49-57): the bottom MLP, then lookup,
+        interaction and the composed top MLP in one kernel that stores the prediction alone
+        (functional.dlrm_score), from the fp32 table or, after quantize_embeddings, the RS_Q8
+        one. Forward only (no grad_fn); compact=True, D 64 or 128, at most 31 slots and a
+        three-layer top MLP with biases ending in one unit, ValueError otherwise."""
+        if not self.compact:
+            raise ValueError("DLRM.score: needs compact=True")
+        cat_features, int_features = x["cat_features"], x["int_features"]
+        int_features = int_features.reshape(-1, self.num_int_fea).float()
+        cat_features = cat_features.reshape(-1, self.num_cat_fea)
+        with torch.no_grad():
+            bmlp_activation = self.bottom_mlp(int_features)
+            return dlrm_score(self.embedding_layer, cat_features, bmlp_activation,
+                              list(self.top_mlp.mlp), self.compact_rows).squeeze(1)
+
     def forward(self, x, training=None, mask=None):
+        if hasattr(self.embedding_layer, "qweight"):
+            # a quantised table (quantize_embeddings) is never trained and has no presort or
+            # exchange: serving only
+            return self.score(x)
         cat_features, int_features = x["cat_features"], x["int_features"]
         int_features = int_features.reshape(-1, self.num_int_fea).float()
         cat_features = cat_features.reshape(-1, self.num_cat_fea)

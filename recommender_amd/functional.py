@@ -465,6 +465,57 @@ def dlrm_top(table_module, ids, dense, layers, rows, composed=False):
                             composed)
 
 
+@torch.no_grad()
+def dlrm_score(table_module, ids, dense, layers, rows) -> torch.Tensor:
+    """DLRM's prediction [B, 1] for serving, in one kernel: lookup, concat with the bottom MLP's
+    `dense`, the compact interaction and the composed top MLP (`layers`, a [n1, n2, 1] chain with
+    biases, over the compact `rows` of its first kernel), nothing but the prediction stored
+    (rs_dlrm_score; rs_dlrm_score_q8 when table_module is a QuantizedEmbedding, whose result
+    equals, bit for bit, the fp32 kernel's over dequantize()). Forward only: the result has no
+    grad_fn. ValueError for shapes outside the kernel: D not 64 or 128, more than 31 slots, a top
+    MLP that is no such chain, or a row width that does not match `rows`."""
+    from .nn import cached_vec_chain_compose, vec_chain_ready
+
+    layers = list(layers)
+    quantised = hasattr(table_module, "qweight")
+    w = table_module.qweight if quantised else table_module.weight
+    D = table_module.output_dim if quantised else w.shape[1]
+    L.require_device(w, "embedding table")
+    ids = _ids_flat(ids)
+    if ids.dim() != 2:
+        raise ValueError(f"dlrm_score: ids must be [B, S], got {tuple(ids.shape)}")
+    B, S = ids.shape
+    F = S + 1
+    if D not in (64, 128):
+        raise ValueError(f"dlrm_score: embedding size {D} is not 64 or 128")
+    if S < 1 or F > 32:
+        raise ValueError(f"dlrm_score: {S} slots; the kernel takes 1 to 31")
+    nz = F * (F - 1) // 2 + D
+    width = rows.numel() if rows is not None else 0
+    if width != (nz + COMPACT_ALIGN - 1) // COMPACT_ALIGN * COMPACT_ALIGN:
+        raise ValueError(f"dlrm_score: compact rows ({width}) do not match the interaction row "
+                         f"({nz})")
+    if not vec_chain_ready(layers, width):
+        raise ValueError("dlrm_score: the top MLP must be three layers with biases ending in "
+                         "one unit")
+    dense = dense.detach().float().contiguous()
+    L.require_device(dense, "dense")
+    if dense.shape != (B, D):
+        raise ValueError(f"dlrm_score: bottom-MLP output must be [{B}, {D}], got "
+                         f"{tuple(dense.shape)}")
+    q, c = cached_vec_chain_compose(layers, rows, width)
+    y = torch.empty(B, 1, device=w.device, dtype=torch.float32)
+    tail = (L.ptr(ids), L.id_dtype_code(ids), S, L.ptr(table_module.slot_offsets), L.ptr(dense), B,
+            L.ptr(q), L.ptr(c), layers[-1].act_code, L.ptr(y), L.ptr(table_module.err_flag),
+            L.stream_ptr(w.device))
+    if quantised:
+        L.call("rs_dlrm_score_q8", L.ptr(w), w.shape[1], w.shape[0], D, *tail)
+    else:
+        _wait_update(table_module)
+        L.call("rs_dlrm_score", L.ptr(w), w.shape[0], D, *tail)
+    return y
+
+
 class _FM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, emb):

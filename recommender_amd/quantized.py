@@ -6,7 +6,9 @@ be scored, or its rows pooled, beside a training job without a second fp32 copy 
 
 `QuantizedEmbedding` / `QuantizedEmbeddingBag` are the forward-only counterparts of `Embedding` /
 `SlabEmbedding` and `EmbeddingBag`; `from_float` builds one from a trained table and
-`quantize_embeddings(model)` swaps a model's tables in place. Nothing here joins autograd.
+`quantize_embeddings(model)` swaps a model's tables in place. DLRM reads a quantised table through
+its scoring kernel (`DLRM.score`, `functional.dlrm_score`: rs_dlrm_score_q8), the other models
+through the lookup. Nothing here joins autograd.
 """
 from __future__ import annotations
 
@@ -128,23 +130,46 @@ def _forward_only_owners():
     return (DeepFM, FeatureTables)
 
 
+def _dlrm_unservable(model) -> str | None:
+    """Which limit of rs_dlrm_score_q8 a DLRM is outside of (None: it can be served)."""
+    from .nn import vec_chain_ready
+
+    D, S = model.embedding_size, model.num_cat_fea
+    if not model.compact:
+        return "compact=False (the kernel forms the compact interaction row)"
+    if D not in (64, 128):
+        return f"embedding size {D} is not 64 or 128"
+    if not 1 <= S <= 31:
+        return f"{S} slots; the kernel takes 1 to 31"
+    layers = list(model.top_mlp.mlp)
+    if not (vec_chain_ready(layers, model.compact_rows.numel())
+            and all(l.act_code == 0 for l in layers[:-1]) and layers[-1].act_code in (0, 1, 2)):
+        return "the top MLP is not three layers with biases ending in one unit"
+    return None
+
+
 def quantize_embeddings(model: nn.Module, forward_only: tuple = ()) -> nn.Module:
     """Swap, in place, every Embedding / SlabEmbedding / EmbeddingBag of `model` for its
     quantised copy and return the model, for use under torch.no_grad(). Only tables whose rows
     are read through their forward alone can be swapped: those of DeepFM (embedding_layer) and of
     FeatureTables (the slab of ESMM / MMOE / BASE), and of the module classes the caller vouches
-    for in forward_only. Everything is checked before anything is swapped. TypeError for
-    DLRM (its fused kernels read weight as fp32), a row-sharded slab, a table with a fused
+    for in forward_only; and DLRM's, whose forward then runs DLRM.score (rs_dlrm_score_q8: lookup,
+    interaction and top MLP in one kernel over the quantised rows) when that kernel can serve it:
+    compact=True, embedding size 64 or 128, at most 31 slots, a three-layer top MLP with biases
+    ending in one unit. Everything is checked before anything is swapped. TypeError for any other
+    DLRM (its other kernels read weight as fp32), a row-sharded slab, a table with a fused
     optimizer still attached, and a table held by a module of any other class."""
     from .ctr.model import DLRM
     from .sharded import ShardedSlabEmbedding
 
-    owners = _forward_only_owners() + tuple(forward_only)
+    owners = _forward_only_owners() + (DLRM,) + tuple(forward_only)
     swaps = []
     for owner in model.modules():
         if isinstance(owner, DLRM):
-            raise TypeError("quantize_embeddings: DLRM's fused kernels read the table's weight as "
-                            "fp32; it cannot run on a quantised table")
+            why = _dlrm_unservable(owner)
+            if why:
+                raise TypeError(f"quantize_embeddings: DLRM's scoring kernel (rs_dlrm_score_q8) "
+                                f"cannot serve this model: {why}")
         for name, child in owner.named_children():
             if isinstance(child, ShardedSlabEmbedding):
                 raise TypeError(f"quantize_embeddings: {name} is a row-sharded slab; its rows are "
