@@ -319,7 +319,11 @@ __global__ __launch_bounds__(256) void aux_bwd_kernel(AuxArgs a, AuxGrad g) {
       for (int f = In + kq; f < kMaxIn; f += 4) T.x[j * kS1 + f] = f == In ? 1.f : 0.f;
       f4 h1[kT1], h2[kT2];
       const float z = aux_forward<H, E>(a, S.w, xv, j, kq, h1, h2);
-      const float d3 = (sb * (m ? 1.f : 0.f)) * (aux_sigm(z) - (set == 0 ? 1.f : 0.f));
+      // rows past L-2 are no aux rows: their factor is exactly 0, not sb·0 — an example without
+      // a valid row has sb = daux/0 and NaN in its aux rows (as the reference), but its hidden
+      // row L-1 takes no gradient from this loss (0, or the upstream under acc_hidden)
+      const float rowf = t <= L - 2 ? sb * (m ? 1.f : 0.f) : 0.f;
+      const float d3 = rowf * (aux_sigm(z) - (set == 0 ? 1.f : 0.f));
       f4 dz2[kT2];
 #pragma unroll
       for (int mm = 0; mm < kT2; ++mm)
@@ -548,7 +552,9 @@ extern "C" int32_t rs_dien_aux_bwd(const float* hidden, const float* pos, const 
 
 // acc_hidden = 1: dhidden holds the upstream gradient of the hidden states (attention + AUGRU)
 // and this loss's part is added to it in place (rows of tiles without a valid step untouched):
-// no zero fill and no separate add pass
+// no zero fill and no separate add pass. An example without a valid aux row (Σ_t m[b,t+1] = 0)
+// has every tile live: NaN (daux/0 · 0, as the reference) in dhidden[b, :L-1], dpos[b, 1:] and
+// dneg[b, 1:]; dhidden[b, L-1] gets exactly 0 added, dpos[b, 0] and dneg[b, 0] are 0
 extern "C" int32_t rs_dien_aux_bwd_acc(const float* hidden, const float* pos, const float* neg,
                                        const uint8_t* mask, int64_t B, int32_t L, int32_t H,
                                        int32_t E, const float* W1, const float* b1, const float* W2,
