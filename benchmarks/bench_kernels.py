@@ -711,6 +711,87 @@ def dlrm_score(iters, out, rounds=5):
         torch.cuda.empty_cache()
 
 
+def group_auc(iters, out, rounds=5):
+    """rs_group_auc against the same counts from torch ops on the GPU (a two-key stable torch.sort,
+    cumsum and index_add_), interleaved in one process: `rounds` rounds of both, each timed with
+    events over `iters` calls; medians reported, every round's time next to them. n = 2^22
+    predictions (512 distinct levels: ties) over 2^16 users with Zipf(1.05) and with uniform
+    membership (int64 user ids), and one group of 2^22 (group = NULL; the torch side then sorts
+    once) with the same 512 levels and with continuous predictions (about 3.7M tie runs). Both sides are checked equal before timing. Bytes: pred, label 4 + 4 and the id 8 per
+    example read, 24 per group written."""
+    from recommender_amd.synthetic import bounded_zipf
+
+    rng = np.random.default_rng(4)
+    dev = torch.device(DEV)
+    st = L.stream_ptr(dev)
+    n, U = 1 << 22, 1 << 16
+    pred = torch.from_numpy((rng.integers(0, 512, n) / 512).astype(np.float32)).to(dev)
+    label = torch.from_numpy((rng.random(n) < 0.3).astype(np.float32)).to(dev)
+    ids = rng.permutation(U).astype(np.int64) * 1_000_003 - (1 << 35)
+    distinct = torch.from_numpy(rng.random(n).astype(np.float32)).to(dev)  # nearly every run of one
+    groups = {"zipf1.05": (torch.from_numpy(ids[bounded_zipf(rng, n, U) % U]).to(dev), pred),
+              "uniform": (torch.from_numpy(ids[rng.integers(0, U, n)]).to(dev), pred),
+              "one group": (None, pred),
+              "one group, continuous predictions": (None, distinct)}
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    cnt = torch.empty(n, dtype=torch.int32, device=dev)
+    pos = torch.empty(n, dtype=torch.int32, device=dev)
+    w2 = torch.empty(n, dtype=torch.int64, device=dev)
+    info = torch.zeros(2, dtype=torch.int32, device=dev)
+    ws = L.scratch(L.lib().rs_group_auc_workspace_size(n), dev)
+
+    def fused(g, pred):
+        L.call("rs_group_auc", L.ptr(pred), L.ptr(label), L.ptr(g), L.RS_ID_I64, n, L.ptr(keys),
+               L.ptr(cnt), L.ptr(pos), L.ptr(w2), L.ptr(info), L.ptr(info[1:]), L.ptr(ws),
+               ws.numel(), st)
+
+    def torch_counts(g, pred):
+        p, perm = torch.sort(pred, stable=True)
+        if g is not None:
+            gs, i2 = torch.sort(g[perm], stable=True)
+            p, perm = p[i2], perm[i2]
+        else:
+            gs = torch.zeros(n, dtype=torch.int64, device=dev)
+        neg = (label[perm] == 0).to(torch.int64)
+        negcum = torch.cat([neg.new_zeros(1), torch.cumsum(neg, 0)])
+        one = torch.ones(1, dtype=torch.bool, device=dev)
+        ghead = torch.cat([one, gs[1:] != gs[:-1]])
+        rhead = ghead | torch.cat([one, p[1:] != p[:-1]])
+        g0 = torch.nonzero(ghead).view(-1)
+        r0 = torch.nonzero(rhead).view(-1)
+        end = torch.full((1,), n, dtype=torch.int64, device=dev)
+        r1, g1 = torch.cat([r0[1:], end]), torch.cat([g0[1:], end])
+        g_of_run = torch.cumsum(ghead.to(torch.int64), 0)[r0] - 1
+        neg_before = negcum[r0] - negcum[g0[g_of_run]]
+        neg_in = negcum[r1] - negcum[r0]
+        contrib = ((r1 - r0) - neg_in) * (2 * neg_before + neg_in)
+        w = torch.zeros(g0.numel(), dtype=torch.int64, device=dev).index_add_(0, g_of_run, contrib)
+        c = g1 - g0
+        return gs[g0], c, c - (negcum[g1] - negcum[g0]), w, r0.numel()
+
+    for what, (g, pred) in groups.items():
+        fused(g, pred)
+        G = int(info[0])
+        *ref, runs = torch_counts(g, pred)
+        assert int(info[1]) == 0 and G == ref[0].numel()
+        for a, b in zip((keys, cnt, pos, w2), ref):
+            assert torch.equal(a[:G].to(torch.int64), b), what
+        variants = [("rs_group_auc", lambda g=g, p=pred: fused(g, p)),
+                    ("torch sort + cumsum", lambda g=g, p=pred: torch_counts(g, p))]
+        times = {name: [] for name, _ in variants}
+        for _ in range(rounds):
+            for name, fn in variants:
+                times[name].append(timed(fn, iters))
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        for name, _ in variants:
+            cfg = {"n": n, "groups": G, "membership": what, "tie_runs": runs,
+                   "rounds_us": [round(t, 1) for t in times[name]]}
+            if name == "rs_group_auc":
+                cfg["torch_over_fused_time"] = round(med["torch sort + cumsum"] / med[name], 3)
+            report(f"group_auc {what}: {name} (interleaved, median of {rounds})", cfg, med[name],
+                   n * (8 + (8 if g is not None else 0)) + 24 * G, out)
+
+
 def criteo(iters, out):
     """Criteo TSV ingestion: line index + parse + vocab lookup over a ~45 MB synthetic text
     (algorithmic bytes: text read once, outputs written once)."""

@@ -1178,6 +1178,43 @@ int32_t rs_auc_update(const float* pred, const float* label, int64_t n, const fl
                       void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Exact per-group AUC counts (GAUC, the metric DIN / DIEN report: Zhou et al. 2018, the
+ * impression-weighted mean of each user's own AUC). Per group the call leaves integers; the
+ * ratio w2 / (2·pos·(n − pos)) and the mean over groups are the host's. One group is the exact
+ * (ungridded) pooled AUC.
+ *
+ * Inputs: pred, label [n] float32; example i is positive iff label[i] != 0 (rs_auc_update's
+ *   rule: -0.0 is negative, a NaN label positive). group [n] of group_dtype RS_ID_I32 / RS_ID_I64:
+ *   any value is legal, negative ones included, equal value = same group; group == NULL: one
+ *   group with key 0 (group_dtype is then not read).
+ * Order of predictions: by float32 value with -0.0 == +0.0; ±inf and subnormals are ordinary
+ *   values. A NaN prediction sets RS_ERRBIT_NONFINITE in err_flag (may be NULL), ranks above +inf
+ *   and ties with every other NaN, so the outputs stay fully defined.
+ * Outputs (capacity n each; n_groups a device int32): groups in ascending signed key order; for
+ *   group j < *n_groups
+ *     group_key[j]  its key,
+ *     group_n[j]    its members,
+ *     group_pos[j]  its positives,
+ *     group_w2[j]   Σ over (positive a, negative b of the group) 2·[pred_a > pred_b] +
+ *                   [pred_a == pred_b]: twice the Mann-Whitney U, ties counting ½, as an integer
+ *                   (<= n²/2 < 2^61).
+ *   Entries at j >= *n_groups are not written.
+ * Determinism: integer arithmetic throughout (the only atomics are 64-bit integer adds), so the
+ *   outputs are a function of the inputs alone.
+ * Limits: 0 <= n <= 2^31 - 1. n == 0 stores *n_groups = 0 and launches nothing else.
+ * Workspace: rs_group_auc_workspace_size(n) bytes (about 40 bytes per example at large n; 0 for n <= 0).
+ * Stream-ordered, no host sync, graph-capturable. Launches: 1 + 12 for the prediction sort, 13
+ *   (int32 groups) or 26 (int64) for the group sort, 1 + 9 + 2 for flags, scans and counts.
+ * Errors: RS_E_INVALID for n outside the limits, a group_dtype that is neither id type, a null
+ *   n_groups, or with n > 0 a null pred / label / output / workspace; RS_E_WORKSPACE for a
+ *   workspace below rs_group_auc_workspace_size(n). */
+size_t rs_group_auc_workspace_size(int64_t n);
+int32_t rs_group_auc(const float* pred, const float* label, const void* group, int32_t group_dtype,
+                     int64_t n, int64_t* group_key, int32_t* group_n, int32_t* group_pos,
+                     unsigned long long* group_w2, int32_t* n_groups, int32_t* err_flag,
+                     void* workspace, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Criteo TSV ingestion (ctr/tfrecord_io.py:15-96), text resident in HBM.
  * rs_line_index: line_starts [n_newlines + 1] int64 (line 0 at byte 0, line k after the k-th
  *   '\n'); *n_newlines device int32; line_starts NULL = count only.
@@ -1318,6 +1355,8 @@ int32_t rs_topk_ip(const float* queries, int64_t q_ld, int32_t n_queries, const 
  * rs_dien_parse: line "label\tuser\titem\tcat\this_items\this_cats", histories '\x02'-separated.
  *   Count pass (item_off NULL): n_hi, n_hc [n_lines] token counts, label. Fill pass: item_hash at
  *   item_off[l] (target) and item_off[l] + 1 + k (history k), cat_hash likewise at cat_off.
+ * rs_dien_users: user_hash [n_lines] = FNV-1a 64 of field 1 (the user) of every line, split as
+ *   rs_dien_parse splits it; a line without six fields sets RS_ERRBIT_OOB and yields the FNV basis.
  * rs_dien_item_cat: cat_of_item[id] = cat id of the item's LAST (item, cat) pair in the stream
  *   (target pair, then zip(history)), -1 for an item without one.
  * rs_dien_encode: target_item / his_item ids (unknown → unk_item), target_cat / his_cat (unknown →
@@ -1355,6 +1394,8 @@ int32_t rs_dien_parse(const uint8_t* text, int64_t n_bytes, const int64_t* line_
                       int64_t n_lines, const int64_t* item_off, const int64_t* cat_off,
                       int32_t* n_hi, int32_t* n_hc, float* label, uint64_t* item_hash,
                       uint64_t* cat_hash, int32_t* err_flag, void* stream);
+int32_t rs_dien_users(const uint8_t* text, int64_t n_bytes, const int64_t* line_starts,
+                      int64_t n_lines, uint64_t* user_hash, int32_t* err_flag, void* stream);
 size_t rs_dien_item_cat_workspace_size(int64_t item_capacity);
 int32_t rs_dien_item_cat(const uint64_t* item_hash, const uint64_t* cat_hash,
                          const int64_t* item_off, const int64_t* cat_off, const int32_t* n_hi,

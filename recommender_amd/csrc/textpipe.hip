@@ -14,6 +14,7 @@
 //                        per-column ids 1.. in first-appearance order (the caller's radix sort)
 //   rs_dien_parse        one wave per line: 6 tab fields, '\x02'-separated histories, count pass
 //                        then a fill pass into line-major ragged token streams
+//   rs_dien_users        the same split: the hash of the user field (the group key of GAUC)
 //   rs_dien_item_cat     item_id2cat_id: the last (item, cat) pair of the stream wins, mapped to ids
 //   rs_dien_encode       lookups (unknown item → unk, unknown cat → error), pad_sequences(post, pre)
 //                        and the DIEN negative history (Philox keyed by (seed, line, position))
@@ -410,6 +411,31 @@ __global__ __launch_bounds__(256) void dien_parse_kernel(
   dien_tokens(lp, lo(5), hi(5), lane, cat_hash + cat_off[line] + 1);
 }
 
+// the user column (field 1) of every line: the key GAUC groups a test file's predictions by
+__global__ __launch_bounds__(256) void dien_users_kernel(
+    const uint8_t* __restrict__ text, int64_t n_bytes, const int64_t* __restrict__ starts,
+    int64_t n_lines, uint64_t* __restrict__ user_hash, int32_t* __restrict__ err_flag) {
+  __shared__ uint8_t stage[4][kStage];
+  __shared__ int32_t fpos[4][8];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t line = (int64_t)blockIdx.x * 4 + wave;
+  if (line >= n_lines) return;
+  int64_t s, e;
+  stripped_line(text, n_bytes, starts, n_lines, line, s, e);
+  const int len = (int)(e - s);
+  const uint8_t* lp = stage_line(text, s, len, stage[wave], lane);
+  int32_t* fp = fpos[wave];
+  const bool ok = dien_fields(lp, len, lane, fp);
+  if (lane != 0) return;
+  if (!ok) {
+    flag_oob(err_flag);
+    user_hash[line] = kFnvBasis;
+    return;
+  }
+  int64_t q;
+  user_hash[line] = hash_token(lp, fp[1], fp[2] - 1, [](uint8_t) { return false; }, &q);
+}
+
 // item_id2cat_id: pairs (item_off[l] + j, cat_off[l] + j) for j < 1 + min(n_hi, n_hc); the pair
 // latest in the stream wins (pass 0: atomicMax of its position, pass 1: the winner writes)
 __global__ __launch_bounds__(256) void dien_pairs_kernel(
@@ -651,6 +677,18 @@ extern "C" int32_t rs_dien_parse(const uint8_t* text, int64_t n_bytes, const int
   dien_parse_kernel<<<(unsigned)ceil_div(n_lines, 4), 256, 0, as_stream(stream)>>>(
       text, n_bytes, line_starts, n_lines, item_off, cat_off, n_hi, n_hc, label, item_hash,
       cat_hash, err_flag);
+  RS_CHECK_LAUNCH();
+  return RS_OK;
+}
+
+extern "C" int32_t rs_dien_users(const uint8_t* text, int64_t n_bytes, const int64_t* line_starts,
+                                 int64_t n_lines, uint64_t* user_hash, int32_t* err_flag,
+                                 void* stream) {
+  RS_CHECK_ARG(n_lines >= 0, "rs_dien_users: bad arguments");
+  if (n_lines == 0) return RS_OK;
+  RS_CHECK_ARG(text && line_starts && user_hash, "rs_dien_users: null pointer");
+  dien_users_kernel<<<(unsigned)ceil_div(n_lines, 4), 256, 0, as_stream(stream)>>>(
+      text, n_bytes, line_starts, n_lines, user_hash, err_flag);
   RS_CHECK_LAUNCH();
   return RS_OK;
 }

@@ -10,6 +10,7 @@ csrc/textpipe.hip does every step:
 
     vocab = DienVocab.build(train_text)                 # util.build_vocab
     feats, label = vocab.encode(text, maxlen=100, sample_negative=True, seed=4)
+    users = read_dien_users(text)                       # per-line user hash: GAUC's group ids
 
 `feats` matches the reference's feature dict batched: target_item / target_cat [n, 1],
 pos_his_item / pos_his_cat (and neg_his_item / neg_his_cat) [n, maxlen], all int32; label
@@ -70,6 +71,21 @@ def read_dien_text(src, device="cuda") -> DienTokens:
            L.ptr(cat_off), L.ptr(n_hi), L.ptr(n_hc), L.ptr(label), L.ptr(item_hash),
            L.ptr(cat_hash), L.ptr(err), st)
     return DienTokens(label, n_hi, n_hc, item_off, cat_off, item_hash, cat_hash)
+
+
+def read_dien_users(src, device="cuda") -> torch.Tensor:
+    """int64 [n]: per line the FNV-1a 64 hash (text.fnv1a64, reinterpreted as signed) of its user
+    field, in line order: the group ids metrics.GroupAUC takes for the file's predictions."""
+    dev = torch.device(device)
+    text = text_to_device(src, dev)
+    starts, n = line_index(text)
+    users = torch.empty(n, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.call("rs_dien_users", L.ptr(text), text.numel(), L.ptr(starts), n, L.ptr(users), L.ptr(err),
+           L.stream_ptr(dev))
+    if n and int(err.item()):
+        raise ValueError("malformed DIEN line (expected 6 tab-separated fields)")
+    return users
 
 
 def _first_appearance_table(hashes: torch.Tensor) -> HashTable:

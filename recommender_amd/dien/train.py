@@ -1,9 +1,11 @@
 """dien/train.py counterpart (reference dien/train.py:12-143): BASE / DIN / DIEN on synthetic
 Amazon-shaped sequences. Flags and defaults as the reference (--gpus --gpu_memory_limit
 --model_type --history_max_length --epochs --train_batch_size --test_batch_size --seed) plus
---item_vocab/--cat_vocab (default 63 001 / 801, Amazon-Electronics-shaped) and
---steps_per_epoch. train_step_dien (dien/train.py:13-24): loss = mean BCE + mean aux; Keras
-Adam on every parameter (embedding tables: exact Keras Adam with the dense decay)."""
+--item_vocab/--cat_vocab (default 63 001 / 801, Amazon-Electronics-shaped),
+--steps_per_epoch and --gauc_users (N > 0: every example gets one of N user ids and the epoch
+line also reports the exact per-user GAUC, metrics.GroupAUC). train_step_dien
+(dien/train.py:13-24): loss = mean BCE + mean aux; Keras Adam on every parameter (embedding
+tables: exact Keras Adam with the dense decay)."""
 from __future__ import annotations
 
 import argparse
@@ -13,7 +15,7 @@ import numpy as np
 import torch
 
 from ..functional import binary_crossentropy
-from ..metrics import AUC
+from ..metrics import AUC, GroupAUC
 from ..optim import KerasAdam, SparseAdam
 from ..steps import StaticKerasAdam, dense_parameters
 from . import DIEN, DIN, BaseModel
@@ -117,6 +119,9 @@ def main(argv=None):
     ap.add_argument("--fused_din", type=int, default=0,
                     help="1: DIN's local activation unit on the fused kernels "
                          "(DIN(fused_activation=True)); 0: the torch path")
+    ap.add_argument("--gauc_users", type=int, default=0,
+                    help="N > 0: draw a user id in [0, N) per example and report the epoch's exact "
+                         "impression-weighted per-user AUC (GAUC); 0: off")
     args = ap.parse_args(argv)
     from ..gemm_tuning import use_tuned_gemms
 
@@ -133,15 +138,20 @@ def main(argv=None):
     step = DIENStep(model)
     rng = np.random.default_rng(args.seed)
     auc = AUC(num_thresholds=20000)  # dien/train.py:43-44
+    gauc = GroupAUC() if args.gauc_users > 0 else None
     static, replay = None, None
     for epoch in range(1, args.epochs + 1):
         t0, tot = time.time(), 0.0
         auc.reset_states()
+        if gauc:
+            gauc.reset_states()
         for _ in range(args.steps_per_epoch):
             f, lab = synthetic_batch(rng, args.train_batch_size, args.history_max_length,
                                      args.item_vocab, args.cat_vocab, args.model_type == "DIEN")
             feats = {k: torch.from_numpy(v).cuda() for k, v in f.items()}
             label = torch.from_numpy(lab).cuda()
+            if gauc:  # drawn after the batch: the batch stream is the one of --gauc_users 0
+                users = torch.from_numpy(rng.integers(0, args.gauc_users, args.train_batch_size)).cuda()
             if args.hip_graph:
                 # static input buffers refilled per batch; the first step runs eagerly (it builds
                 # the optimizer state), the second captures the graph that later steps replay
@@ -159,8 +169,11 @@ def main(argv=None):
             else:
                 tot += float(step(feats, label)[0])
                 auc.update_state(label, step.last_pred)
+            if gauc:
+                gauc.update_state(label, step.last_pred, users)
         torch.cuda.synchronize()
-        print(f"epoch {epoch} loss {tot / args.steps_per_epoch:.4f} auc {auc.result():.4f} "
+        extra = f"gauc {gauc.result():.4f} " if gauc else ""
+        print(f"epoch {epoch} loss {tot / args.steps_per_epoch:.4f} auc {auc.result():.4f} {extra}"
               f"{args.steps_per_epoch * args.train_batch_size / (time.time() - t0):.0f} ex/s")
 
 

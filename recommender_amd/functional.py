@@ -850,6 +850,43 @@ def topk_inner_product(queries, items, k: int, exclude=None, exclude_base: int =
     return idx, val
 
 
+def group_auc_counts(pred, label, group=None):
+    """(keys int64 [G], n int32 [G], pos int32 [G], w2 int64 [G]) by rs_group_auc: per group
+    (ascending key) its members, its positives (label != 0) and w2 = Σ over its (positive,
+    negative) pairs of 2·[p_pos > p_neg] + [p_pos == p_neg], twice the Mann-Whitney U, so the
+    group's exact AUC is w2 / (2·pos·(n − pos)). group: int32 / int64 ids, any value; None: one
+    group with key 0. Exact integers, identical from run to run. One sync (the group count and the
+    error flag); a NaN prediction raises ValueError. No autograd."""
+    L.require_device(pred, "pred")
+    dev = pred.device
+    p = pred.detach().reshape(-1).float().contiguous()
+    y = label.detach().reshape(-1).float().contiguous()
+    n = p.numel()
+    if y.numel() != n:
+        raise ValueError("group_auc_counts: pred and label sizes differ")
+    g, dt = None, L.RS_ID_I32
+    if group is not None:
+        g = group.detach().reshape(-1).contiguous()
+        dt = L.id_dtype_code(g)
+        if g.numel() != n:
+            raise ValueError("group_auc_counts: pred and group sizes differ")
+    if y.device != dev or (g is not None and g.device != dev):
+        raise ValueError("group_auc_counts: inputs on different devices")
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    cnt = torch.empty(n, dtype=torch.int32, device=dev)
+    pos = torch.empty(n, dtype=torch.int32, device=dev)
+    w2 = torch.empty(n, dtype=torch.int64, device=dev)
+    info = torch.zeros(2, dtype=torch.int32, device=dev)  # n_groups, error flag
+    need = L.lib().rs_group_auc_workspace_size(n)
+    ws = L.scratch(need, dev)
+    L.call("rs_group_auc", L.ptr(p), L.ptr(y), L.ptr(g), dt, n, L.ptr(keys), L.ptr(cnt), L.ptr(pos),
+           L.ptr(w2), L.ptr(info), L.ptr(info[1:]), L.ptr(ws), ws.numel(), L.stream_ptr(dev))
+    G, err = info.tolist()
+    if err:
+        raise ValueError("group_auc_counts: NaN prediction")
+    return keys[:G], cnt[:G], pos[:G], w2[:G]
+
+
 # ---- row-wise int8 tables (include/recsys_hip.h a-1c): forward only, no autograd -----------
 def q8_row_bytes(dim: int) -> int:
     """The default row stride of a quantised table of `dim` columns (rs_q8_row_bytes)."""

@@ -1,11 +1,17 @@
-"""Device metrics: Keras' thresholded AUC.
+"""Device metrics: Keras' thresholded AUC, and the exact per-group AUC.
 
 AUC(num_thresholds=200, curve='ROC', summation_method='interpolation') mirrors
 keras.metrics.AUC [3p TF 2.2] as the reference uses it (ctr/train.py:86 default 200,
 dien/train.py:43-44 20000, esmm/train.py:164 10000): update_state(y_true, y_pred) on device
 (rs_auc_update: one bucket histogram pass), result() from the exact int64 counts, reset_states().
-Curves: ROC (interpolation / minoring / majoring) and PR (interpolation, Davis & Goadrich)."""
+Curves: ROC (interpolation / minoring / majoring) and PR (interpolation, Davis & Goadrich).
+
+GroupAUC / ExactAUC: the exact Mann-Whitney AUC per group (GAUC, per user) or pooled, from
+rs_group_auc's integer pair counts; the ratios and their weighted mean are formed on the host."""
 from __future__ import annotations
+
+import math
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -94,3 +100,103 @@ class AUC:
     def reset_states(self):
         self.counts.zero_()
         self.err_flag.zero_()
+
+
+def gauc_from_counts(n: np.ndarray, pos: np.ndarray, w2: np.ndarray, weight: str = "impressions") -> float:
+    """Σ_u w_u·AUC_u / Σ_u w_u over the groups with 0 < pos < n, AUC_u = w2 / (2·pos·(n − pos))
+    and w_u = n ("impressions"), pos ("positives") or 1 ("uniform"), in float64 from the exact
+    integers; 0.0 when no group qualifies (auc_from_counts' empty-ratio convention). The value is
+    the exact rational rounded once: every term enters math.fsum as its correctly rounded
+    quotient plus that quotient's remainder, the sum is kept as two floats, and the only
+    rounding that counts is the last division."""
+    if weight not in GroupAUC.WEIGHTS:
+        raise ValueError(f"weight must be one of {GroupAUC.WEIGHTS}, got {weight!r}")
+    parts, den = [], 0
+    for nu, pu, wu in zip(n.tolist(), pos.tolist(), w2.tolist()):
+        if 0 < pu < nu:
+            w = nu if weight == "impressions" else pu if weight == "positives" else 1
+            t, d = w * wu, 2 * pu * (nu - pu)
+            q = t / d  # int / int: correctly rounded
+            qn, qd = q.as_integer_ratio()
+            parts += [q, (t * qd - qn * d) / (d * qd)]
+            den += w
+    if not den:
+        return 0.0
+    hi = math.fsum(parts)
+    lo = math.fsum(parts + [-hi])
+    return float((Fraction(hi) + Fraction(lo)) / den)
+
+
+class GroupAUC:
+    """GAUC, the per-user AUC DIN / DIEN are judged by: every group's exact Mann-Whitney AUC
+    (ties ½; rs_group_auc's integer counts) averaged with weight n, pos or 1; groups whose examples
+    are all of one label are left out. update_state(y_true, y_pred, group) appends to device
+    buffers (capacity doubles, nothing moves to the host); a group's examples may come in any
+    number of calls and any order. groups() -> (keys, n, pos, w2) as NumPy; result() -> float."""
+    WEIGHTS = ("impressions", "positives", "uniform")
+
+    def __init__(self, weight: str = "impressions", name: str | None = None, device="cuda"):
+        if weight not in self.WEIGHTS:
+            raise ValueError(f"weight must be one of {self.WEIGHTS}, got {weight!r}")
+        self.weight = weight
+        self.name = name
+        self.device = torch.device(device)
+        self.reset_states()
+
+    def reset_states(self):
+        self.size = 0
+        self._pred = torch.empty(0, dtype=torch.float32, device=self.device)
+        self._label = torch.empty(0, dtype=torch.float32, device=self.device)
+        self._group = torch.empty(0, dtype=torch.int64, device=self.device)
+
+    def _append(self, cols):
+        k = cols[0].numel()
+        if self.size + k > self._pred.numel():
+            cap = max(2 * self._pred.numel(), self.size + k, 1024)
+            for name in ("_pred", "_label", "_group"):
+                old = getattr(self, name)
+                new = torch.empty(cap, dtype=old.dtype, device=self.device)
+                new[:self.size] = old[:self.size]
+                setattr(self, name, new)
+        for buf, c in zip((self._pred, self._label, self._group), cols):
+            buf[self.size:self.size + k] = c
+        self.size += k
+
+    def update_state(self, y_true, y_pred, group):
+        p = torch.as_tensor(y_pred, device=self.device).detach().reshape(-1).float()
+        y = torch.as_tensor(y_true, device=self.device).detach().reshape(-1).float()
+        g = torch.as_tensor(group, device=self.device).reshape(-1).to(torch.int64)
+        if not p.numel() == y.numel() == g.numel():
+            raise ValueError("y_true, y_pred and group sizes differ")
+        self._append((p, y, g))
+
+    def _counts(self):
+        from .functional import group_auc_counts
+
+        s = self.size
+        return group_auc_counts(self._pred[:s], self._label[:s], self._group[:s])
+
+    def groups(self):
+        return tuple(t.cpu().numpy() for t in self._counts())
+
+    def result(self) -> float:
+        _, n, pos, w2 = self.groups()
+        return gauc_from_counts(n, pos, w2, self.weight)
+
+
+class ExactAUC(GroupAUC):
+    """The exact pooled AUC (Mann-Whitney, ties ½; no threshold grid): GroupAUC's one-group case,
+    update_state(y_true, y_pred). 0.0 while either label is absent."""
+
+    def __init__(self, name: str | None = None, device="cuda"):
+        super().__init__("uniform", name, device)
+
+    def update_state(self, y_true, y_pred):
+        p = torch.as_tensor(y_pred, device=self.device).reshape(-1)
+        super().update_state(y_true, p, torch.zeros(p.numel(), dtype=torch.int64, device=self.device))
+
+    def _counts(self):
+        from .functional import group_auc_counts
+
+        s = self.size
+        return group_auc_counts(self._pred[:s], self._label[:s], None)
