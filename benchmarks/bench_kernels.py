@@ -311,6 +311,80 @@ def topk_ip(iters, out, rounds=5):
     bench("eges_like", q, x, 10, None, 1)
 
 
+def ivf_topk(iters, out, rounds=5):
+    """IVF retrieval (retrieval.IVFIndex.search: coarse rs_topk_ip over the centroids, then
+    rs_ivf_topk_ip) against the exhaustive rs_topk_ip at the EGES-like shape of topk_ip():
+    65 536 queries x 2^20 items, D 160, k 10, nlist 1024, nprobe 1, 4, 16, 64. Interleaved in one
+    process: `rounds` rounds of the exact call and every nprobe, one launch each, timed with
+    events; medians reported with every round next to them. Per line: recall@10 against the exact
+    result, the mean fraction of the catalogue a query scans, the index build time (one build,
+    10 Lloyd iterations, host-timed after a synchronise).
+    Data: (a) a Gaussian mixture, 4096 centres, unit-norm rows; (b) unstructured normal rows.
+    Queries are catalogue rows."""
+    from recommender_amd.functional import topk_inner_product
+    from recommender_amd.retrieval import IVFIndex
+    import time
+
+    N, Q, D, k, nlist = 1 << 20, 65536, 160, 10, 1024
+    gen = torch.Generator(device=DEV).manual_seed(4)
+    s = torch.cuda.current_stream()
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record(s)
+        r = fn()
+        e1.record(s)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), r
+
+    def bench(name, x):
+        q = x[torch.randint(0, N, (Q,), device=DEV, generator=gen)].contiguous()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        index = IVFIndex.build(x, nlist)
+        torch.cuda.synchronize()
+        build_ms = (time.perf_counter() - t0) * 1e3
+        sizes = index.list_sizes
+        fns = {"exact": lambda: topk_inner_product(q, x, k, with_scores=False)[0]}
+        for nprobe in (1, 4, 16, 64):
+            fns[nprobe] = lambda nprobe=nprobe: index.search(q, k, nprobe, with_scores=False)[0]
+        exact = fns["exact"]()
+        stats = {}
+        for nprobe in (1, 4, 16, 64):
+            got = fns[nprobe]()
+            recall = float((got[:, :, None] == exact[:, None, :]).any(1).float().mean())
+            scanned = float(sizes[index.probes(q, nprobe).long()].sum(1).float().mean()) / N
+            stats[nprobe] = (recall, scanned)
+        times = {label: [] for label in fns}
+        for _ in range(rounds):
+            for label, fn in fns.items():
+                times[label].append(once(fn)[0])
+        me = float(np.median(times["exact"]))
+        for nprobe in (1, 4, 16, 64):
+            mi = float(np.median(times[nprobe]))
+            line = {"kernel": "IVFIndex.search vs rs_topk_ip",
+                    "config": {"data": name, "queries": Q, "items": N, "D": D, "k": k,
+                               "nlist": nlist, "nprobe": nprobe},
+                    "exact_ms": round(me, 3), "ivf_ms": round(mi, 3), "speedup": round(me / mi, 2),
+                    "ivf_below_fastest_exact_round": bool(mi < min(times["exact"])),
+                    "recall_at_10": round(stats[nprobe][0], 4),
+                    "scanned_fraction": round(stats[nprobe][1], 5),
+                    "build_ms": round(build_ms, 1),
+                    "largest_list": int(sizes.max()), "empty_lists": int((sizes == 0).sum()),
+                    "exact_rounds_ms": [round(t, 3) for t in times["exact"]],
+                    "ivf_rounds_ms": [round(t, 3) for t in times[nprobe]]}
+            out.append(line)
+            print(json.dumps(line), flush=True)
+
+    centres = torch.nn.functional.normalize(torch.randn(4096, D, device=DEV, generator=gen))
+    member = torch.randint(0, 4096, (N,), device=DEV, generator=gen)
+    x = centres[member] + 0.05 * torch.randn(N, D, device=DEV, generator=gen)
+    bench("gaussian_mixture_4096", torch.nn.functional.normalize(x).contiguous())
+    del x, centres, member
+    bench("normal", torch.randn(N, D, device=DEV, generator=gen))
+
+
 def din_activation(iters, out, rounds=5):
     """DIN's LocalActivationUnit fused (csrc/din_activation.hip) against the unfused torch unit
     with the same weights, at the cfg3 shape (B 4096, L 100, D 36), with synthetic_batch history

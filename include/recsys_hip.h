@@ -1335,6 +1335,59 @@ int32_t rs_topk_ip(const float* queries, int64_t q_ld, int32_t n_queries, const 
                    float* out_scores, void* workspace, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * IVF (inverted-file) top-k inner-product retrieval: rs_topk_ip restricted, per query, to the
+ * inverted lists the query probes. vectors [n_items, v_ld] holds the catalogue list-major (list l
+ * is the stored rows [list_offsets[l], list_offsets[l+1])), item_ids [n_items] the id every
+ * stored row is reported under (NULL: the row number), probes [n_queries, nprobe] (int32,
+ * contiguous) the lists of every query. recommender_amd/retrieval.py builds such an index.
+ *
+ * Candidates of query r: the stored rows j in [list_offsets[l], list_offsets[l+1]) for every
+ *   l = probes[r, p] with 0 <= l < n_lists. Any other probe value is ignored; -1 is the "no
+ *   list" value. A list that appears twice in a row contributes its rows twice. The id of a
+ *   candidate is item_ids[j]: it is what out_items reports, what breaks ties (ascending) and
+ *   what excl_items (CSR row excl_base + r) and excl_one[r] are matched against. Ids lie in
+ *   [0, 2^31 - 1); they need not be sorted or distinct and are not checked.
+ * Score, order, NaN / ±0 handling, padding (-1, -inf) and out_scores == NULL: rs_topk_ip's, word
+ *   for word (the same device code). The bits of a score do not depend on which queries share
+ *   a block, on nprobe, list_splits or k. So the result equals the exhaustive result restricted
+ *   to the probed lists, bit for bit, and with every list probed once rs_topk_ip's itself (over
+ *   distinct ids).
+ * Bad offsets: a list's range is clipped to [0, n_items]; a range with hi <= lo is empty. No
+ *   offset makes the kernel read outside vectors or item_ids.
+ * Work: one block takes one list, at most 32 of the queries that probe it (gathered through an
+ *   index into the LDS query tile) and one of list_splits equal sub-ranges of the list (the last
+ *   takes the remainder), and leaves k pairs per query in the workspace slot of (query, probe,
+ *   sub-range). The work list is made on the device: rs_sort_ids groups the flattened probes by
+ *   list, a few small kernels turn the per-list counts into tiles of at most 32 queries, and the
+ *   grid is the host-known bound (min(n_lists, Q·nprobe) + Q·nprobe / 32 + 1) · list_splits,
+ *   whose surplus blocks return. One wave per query then merges its nprobe · list_splits sorted
+ *   lists by the same order, skipping the probes that name no list.
+ * list_splits: 0 lets the call choose (at most 8) from n_queries, nprobe, n_lists, n_items and
+ *   the CU count; >= 1 forces that many. nprobe in [1, 64]; nprobe * list_splits <=
+ *   RS_IVF_MAX_SLOTS. The result does not depend on list_splits.
+ * Determinism: the result is a function of the inputs only. No block waits for another and the
+ *   host never synchronises: the call can be captured in a HIP graph on one stream.
+ * Limits: 1 <= k <= 64, 1 <= dim <= 256, q_ld, v_ld >= dim, n_items < 2^31, n_lists < 2^31 - 1,
+ *   n_queries * nprobe < 2^31. Access width by alignment of vectors / v_ld / dim as rs_topk_ip.
+ *   n_queries == 0 is a no-op; n_items == 0 or n_lists == 0 writes all padding (no workspace).
+ * Workspace: rs_ivf_topk_ip_workspace_size with the same five arguments (0 for sizes the call
+ *   refuses or needs none for).
+ * Errors: RS_E_INVALID for null queries / probes / list_offsets / vectors / out_items, k, dim,
+ *   ld or nprobe out of range, a negative size, n_items >= 2^31, a workspace that is too small,
+ *   list_splits < 0 or nprobe * list_splits > RS_IVF_MAX_SLOTS. */
+#define RS_IVF_MAX_SLOTS 1024
+size_t rs_ivf_topk_ip_workspace_size(int32_t n_queries, int32_t nprobe, int64_t n_lists,
+                                     int32_t k, int32_t list_splits);
+int32_t rs_ivf_topk_ip(const float* queries, int64_t q_ld, int32_t n_queries,
+                       const int32_t* probes, int32_t nprobe, const int64_t* list_offsets,
+                       int64_t n_lists, const int32_t* item_ids, const float* vectors,
+                       int64_t v_ld, int64_t n_items, int32_t dim, int64_t excl_base,
+                       const int64_t* excl_indptr, const int32_t* excl_items,
+                       const int32_t* excl_one, int32_t k, int32_t list_splits,
+                       int32_t* out_items, float* out_scores, void* workspace, size_t ws_bytes,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Ali-CCP and Amazon (DIEN) text → ids (esmm/process_public_dataset.py:40-153,
  * dien/util.py:4-37, dien/data_loader.py:27-63). Lines come from rs_line_index; each line is
  * str.strip()ped as the reference does.

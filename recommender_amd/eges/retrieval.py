@@ -5,7 +5,8 @@ item_hidden    [n_items, D]: model.get_hidden over every item id, in chunks, wit
                GES / EGES take the items' category and brand ids; DeepWalk takes ids only.
 similar_items  (idx int32 [Q, k], scores fp32 [Q, k]): per query item its k best other items
                (the query item itself is excluded). Inner product: normalise the rows first for
-               cosine similarity.
+               cosine similarity. index= (retrieval.IVFIndex.build(hidden, nlist)) searches
+               the nprobe nearest lists instead of the whole catalogue.
 """
 from __future__ import annotations
 
@@ -35,6 +36,11 @@ def item_hidden(model, item2cat=None, item2brand=None, batch: int = 65536) -> to
     return out
 
 
-def similar_items(hidden: torch.Tensor, query_items: torch.Tensor, k: int):
+def similar_items(hidden: torch.Tensor, query_items: torch.Tensor, k: int, index=None,
+                  nprobe: int = 8):
+    """index: a retrieval.IVFIndex over `hidden`: the search covers the nprobe lists nearest to
+    each query only (approximate; nprobe = index.nlist is exact). None: exhaustive."""
     query_items = torch.as_tensor(query_items).to(hidden.device)
+    if index is not None:
+        return index.search(hidden[query_items.long()], k, nprobe, exclude_one=query_items)
     return topk_inner_product(hidden[query_items.long()], hidden, k, exclude_one=query_items)

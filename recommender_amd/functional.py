@@ -827,19 +827,7 @@ def topk_inner_product(queries, items, k: int, exclude=None, exclude_base: int =
     dev = q.device
     Q, dim = q.shape
     n_items = x.shape[0]
-    ip = it = one = None
-    if exclude is not None:
-        ip, it = exclude
-        L.require_device(ip, "exclude indptr")
-        L.require_device(it, "exclude indices")
-        ip, it = ip.to(torch.int64).contiguous(), it.to(torch.int32).contiguous()
-        if ip.numel() < exclude_base + Q + 1:
-            raise ValueError("topk_inner_product: exclude indptr shorter than exclude_base + Q + 1")
-    if exclude_one is not None:
-        L.require_device(exclude_one, "exclude_one")
-        one = exclude_one.to(torch.int32).contiguous()
-        if one.numel() != Q:
-            raise ValueError("topk_inner_product: exclude_one must hold one id per query")
+    ip, it, one = _exclusion_args("topk_inner_product", Q, exclude, exclude_base, exclude_one)
     idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
     val = torch.empty(Q, k, device=dev) if with_scores else None
     need = L.lib().rs_topk_ip_workspace_size(Q, n_items, k, n_splits)
@@ -847,6 +835,74 @@ def topk_inner_product(queries, items, k: int, exclude=None, exclude_base: int =
     L.call("rs_topk_ip", L.ptr(q), q_ld, Q, L.ptr(x), i_ld, n_items, dim, exclude_base,
            L.ptr(ip), L.ptr(it), L.ptr(one), k, n_splits, L.ptr(idx), L.ptr(val), L.ptr(ws),
            ws.numel() if ws is not None else 0, L.stream_ptr(dev))
+    return idx, val
+
+
+def _exclusion_args(fn, Q, exclude, exclude_base, exclude_one):
+    """(indptr int64, indices int32, one int32) device tensors (or None) of a top-k call."""
+    ip = it = one = None
+    if exclude is not None:
+        ip, it = exclude
+        L.require_device(ip, "exclude indptr")
+        L.require_device(it, "exclude indices")
+        ip, it = ip.to(torch.int64).contiguous(), it.to(torch.int32).contiguous()
+        if ip.numel() < exclude_base + Q + 1:
+            raise ValueError(f"{fn}: exclude indptr shorter than exclude_base + Q + 1")
+    if exclude_one is not None:
+        L.require_device(exclude_one, "exclude_one")
+        one = exclude_one.to(torch.int32).contiguous()
+        if one.numel() != Q:
+            raise ValueError(f"{fn}: exclude_one must hold one id per query")
+    return ip, it, one
+
+
+def ivf_topk_inner_product(queries, probes, list_offsets, item_ids, vectors, k: int,
+                           exclude=None, exclude_base: int = 0, exclude_one=None,
+                           with_scores: bool = True, list_splits: int = 0):
+    """(idx int32 [Q, k], scores fp32 [Q, k]) by rs_ivf_topk_ip: topk_inner_product restricted,
+    per query, to the inverted lists it probes. probes int32 [Q, nprobe]: list ids, anything
+    outside [0, n_lists) (-1) is no list. list_offsets int64 [n_lists + 1]: list l is the rows
+    [list_offsets[l], list_offsets[l+1]) of vectors [n, dim]. item_ids int32 [n] or None: the id
+    each stored row is reported, tie-broken and excluded under (None: the row number). The
+    exclusion arguments are topk_inner_product's, in reported ids. list_splits: 0 = chosen by the
+    call, >= 1 forces that many sub-ranges per list; the result does not depend on it.
+    retrieval.IVFIndex builds and searches such an index. No autograd."""
+    fn = "ivf_topk_inner_product"
+    q, q_ld = _row_major(queries, "queries")
+    x, v_ld = _row_major(vectors, "vectors")
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"{fn}: queries are {q.shape[1]} wide, vectors {x.shape[1]}")
+    dev = q.device
+    Q, dim = q.shape
+    n = x.shape[0]
+    for t, name in ((probes, "probes"), (list_offsets, "list_offsets")):
+        L.require_device(t, name)
+        if t.device != dev:
+            raise ValueError(f"{fn}: queries and {name} on different devices")
+    if x.device != dev:
+        raise ValueError(f"{fn}: queries and vectors on different devices")
+    if probes.dim() != 2 or probes.shape[0] != Q:
+        raise ValueError(f"{fn}: probes must be [Q, nprobe], got shape {tuple(probes.shape)}")
+    pr = probes.to(torch.int32).contiguous()
+    off = list_offsets.to(torch.int64).contiguous()
+    if off.dim() != 1 or off.numel() < 1:
+        raise ValueError(f"{fn}: list_offsets must be 1-D with n_lists + 1 entries")
+    n_lists, nprobe = off.numel() - 1, pr.shape[1]
+    ids = None
+    if item_ids is not None:
+        L.require_device(item_ids, "item_ids")
+        ids = item_ids.to(torch.int32).contiguous()
+        if ids.numel() != n or ids.device != dev:
+            raise ValueError(f"{fn}: item_ids must hold one id per row of vectors, on its device")
+    ip, it, one = _exclusion_args(fn, Q, exclude, exclude_base, exclude_one)
+    idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    val = torch.empty(Q, k, device=dev) if with_scores else None
+    need = L.lib().rs_ivf_topk_ip_workspace_size(Q, nprobe, n_lists, k, list_splits)
+    ws = L.workspace("functional.ivf_topk_ip", need, dev) if need else None
+    L.call("rs_ivf_topk_ip", L.ptr(q), q_ld, Q, L.ptr(pr), nprobe, L.ptr(off), n_lists,
+           L.ptr(ids), L.ptr(x), v_ld, n, dim, exclude_base, L.ptr(ip), L.ptr(it), L.ptr(one), k,
+           list_splits, L.ptr(idx), L.ptr(val), L.ptr(ws), ws.numel() if ws is not None else 0,
+           L.stream_ptr(dev))
     return idx, val
 
 

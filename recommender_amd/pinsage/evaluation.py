@@ -13,7 +13,10 @@ recommend        evaluation.py:27-51  latest item per user (rs_latest_item) → 
                  fused=True: one rs_topk_ip call (functional.topk_inner_product) on the latest
                  items' rows with the u2i CSR as the exclusion: no score matrix, no
                  n_items ≤ 2^20 limit; scores are the ascending fmaf chain, so a near-tie may
-                 rank differently than under the GEMM's rounding.
+                 rank differently than under the GEMM's rounding. With index= (a
+                 retrieval.IVFIndex over item_reprs) only the nprobe lists nearest to each
+                 latest item are scored, with the same exclusion (approximate; nprobe =
+                 index.nlist gives the fused result).
 hit_rate_eval    evaluation.py:54-65  mean over users of any(recommended ∈ ground truth).
 train_test_split_by_time / build_val_test_matrix   util.py:5-39 (numpy instead of pandas:
                  per user by time, the last rating → test and the second-to-last → val;
@@ -108,11 +111,17 @@ def masked_topk(scores: torch.Tensor, top_k: int, user_base: int = 0,
 
 def recommend(full_graph: HeteroGraph, top_k: int, item_reprs: torch.Tensor,
               user2item_etype=None, utype=None, timestamp: str = "timestamp",
-              batch_size: int = 32, fused: bool = False):
+              batch_size: int = 32, fused: bool = False, index=None, nprobe: int = 8):
     L.require_device(item_reprs, "item_reprs")
     reprs = item_reprs.float().contiguous()
     n_users, n_items = full_graph.n_users, reprs.shape[0]
     latest = latest_items(full_graph, timestamp)
+    if index is not None:
+        if not fused:
+            raise ValueError("recommend: index= goes with fused=True")
+        return index.search(reprs[latest.long()], top_k, nprobe,
+                            exclude=(full_graph.u2i_indptr, full_graph.u2i),
+                            with_scores=False)[0]
     if fused:
         from ..functional import topk_inner_product
 

@@ -29,7 +29,8 @@ under that global norm, layers.py:28-29); None leaves fc_2's output as it is.
 
 `python -m recommender_amd.pinsage.inference [--graph ml1m|ml20m] [--out reprs.npy]` runs it on
 the synthetic MovieLens graph of pinsage/train.py; `--neighbors K --neighbors-out nbrs.npy` adds
-each item's K nearest items by inner product (rs_topk_ip, the item itself excluded).
+each item's K nearest items by inner product (rs_topk_ip, the item itself excluded);
+`--neighbors-nlist N --neighbors-nprobe P` searches them through an IVF index (retrieval.py).
 """
 from __future__ import annotations
 
@@ -220,6 +221,10 @@ def main(argv=None):
     ap.add_argument("--neighbors-out", default=None, metavar="FILE",
                     help="write the [n_items, K] int32 neighbour ids (best first, the item "
                          "itself excluded, -1 = none left) to this .npy file")
+    ap.add_argument("--neighbors-nlist", type=int, default=0, metavar="N",
+                    help="search the neighbours through an IVF index of N lists (0: exact)")
+    ap.add_argument("--neighbors-nprobe", type=int, default=8, metavar="P",
+                    help="lists searched per item with --neighbors-nlist")
     args = ap.parse_args(argv)
     if bool(args.neighbors) != bool(args.neighbors_out):
         ap.error("--neighbors K and --neighbors-out FILE go together")
@@ -245,8 +250,15 @@ def main(argv=None):
         from ..functional import topk_inner_product
 
         own = torch.arange(reprs.shape[0], dtype=torch.int32, device=reprs.device)
-        nbrs, _ = topk_inner_product(reprs, reprs, args.neighbors, exclude_one=own,
-                                     with_scores=False)
+        if args.neighbors_nlist > 0:
+            from ..retrieval import IVFIndex
+
+            index = IVFIndex.build(reprs, args.neighbors_nlist)
+            nbrs, _ = index.search(reprs, args.neighbors, args.neighbors_nprobe, exclude_one=own,
+                                   with_scores=False)
+        else:
+            nbrs, _ = topk_inner_product(reprs, reprs, args.neighbors, exclude_one=own,
+                                         with_scores=False)
         np.save(args.neighbors_out, nbrs.cpu().numpy())
         print(f"wrote {args.neighbors_out}")
     return reprs
