@@ -311,6 +311,94 @@ def topk_ip(iters, out, rounds=5):
     bench("eges_like", q, x, 10, None, 1)
 
 
+def item_softmax(iters, out, rounds=3):
+    """functional.item_softmax_loss (rs_item_softmax_fwd + _bwd, no [B, M] matrix) against the
+    torch composition logsumexp(q @ v.T * inv_temp - log_q, 1) - diagonal under autograd, forward
+    + backward, interleaved in one process: `rounds` rounds of both, each timed with events over
+    its launches; medians and every round's time, and each side's peak memory over the inputs
+    (torch.cuda.max_memory_allocated). A torch side that cannot allocate is reported as such and
+    skipped. B = M = 8 192; B = M = 32 768; B = 4 096 over M = 2^20; all at D = 128."""
+    from recommender_amd.functional import item_softmax_loss
+
+    inv_temp = 10.0
+    gen = torch.Generator(device=DEV).manual_seed(4)
+
+    def bench(B, M, D, n_iter):
+        q = (torch.randn(B, D, device=DEV, generator=gen) / D ** 0.5).requires_grad_()
+        v = (torch.randn(M, D, device=DEV, generator=gen) / D ** 0.5).requires_grad_()
+        log_q = torch.randn(M, device=DEV, generator=gen)
+        t = torch.randint(0, M, (B,), device=DEV, generator=gen, dtype=torch.int32)
+        tl = t.long()
+        rows = torch.arange(B, device=DEV)
+
+        def fused():
+            q.grad = v.grad = None
+            loss = item_softmax_loss(q, v, t, temperature=1.0 / inv_temp, log_q=log_q)
+            loss.backward()
+            return loss.detach()
+
+        def base():
+            q.grad = v.grad = None
+            z = torch.matmul(q, v.t()) * inv_temp - log_q[None]
+            loss = (torch.logsumexp(z, 1) - z[rows, tl]).mean()
+            loss.backward()
+            return loss.detach()
+
+        def peak(fn):
+            q.grad = v.grad = None
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            m0 = torch.cuda.memory_allocated()
+            r = fn()
+            torch.cuda.synchronize()
+            return r, torch.cuda.max_memory_allocated() - m0
+
+        lf, peak_f = peak(fused)
+        gq = q.grad.clone()
+        try:
+            lb, peak_b = peak(base)
+            diff = {"loss_diff": abs(float(lf) - float(lb)),
+                    "dq_max_diff": float((gq - q.grad).abs().max())}
+            sides = (("base", base), ("fused", fused))
+        except torch.OutOfMemoryError:
+            q.grad = v.grad = None
+            torch.cuda.empty_cache()
+            peak_b, diff, sides = None, {}, (("fused", fused),)
+        times = {"base": [], "fused": []}
+        s = torch.cuda.current_stream()
+        for _ in range(rounds):
+            for label, fn in sides:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record(s)
+                for _ in range(n_iter):
+                    fn()
+                e1.record(s)
+                torch.cuda.synchronize()
+                times[label].append(e0.elapsed_time(e1) / n_iter)
+        mf = float(np.median(times["fused"]))
+        line = {"kernel": "item_softmax_loss fwd+bwd vs torch logsumexp(q @ v.T) autograd",
+                "config": {"B": B, "M": M, "D": D, "inv_temp": inv_temp},
+                "fused_ms": round(mf, 3), "fused_peak_MiB": round(peak_f / 2 ** 20, 1),
+                "fused_rounds_ms": [round(x, 3) for x in times["fused"]],
+                # five tile GEMMs of 2·B·M·D flop each
+                "fused_TF": round(10.0 * B * M * D / (mf * 1e-3) / 1e12, 2)}
+        if peak_b is None:
+            line["base"] = "torch side could not allocate its [B, M] tensors: skipped"
+        else:
+            mb = float(np.median(times["base"]))
+            line.update({"base_ms": round(mb, 3), "base_peak_MiB": round(peak_b / 2 ** 20, 1),
+                         "base_rounds_ms": [round(x, 3) for x in times["base"]],
+                         "speedup": round(mb / mf, 2), **diff})
+        out.append(line)
+        print(json.dumps(line), flush=True)
+        q.grad = v.grad = None
+
+    bench(8192, 8192, 128, max(1, iters // 4))
+    bench(32768, 32768, 128, 1)
+    bench(4096, 1 << 20, 128, 1)
+
+
 def ivf_topk(iters, out, rounds=5):
     """IVF retrieval (retrieval.IVFIndex.search: coarse rs_topk_ip over the centroids, then
     rs_ivf_topk_ip) against the exhaustive rs_topk_ip at the EGES-like shape of topk_ip():

@@ -1388,6 +1388,69 @@ int32_t rs_ivf_topk_ip(const float* queries, int64_t q_ld, int32_t n_queries,
                        void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Softmax cross-entropy over item rows: the loss of query row r against every row of an item
+ * matrix, with row t(r) the positive, forward and backward, with no [n_queries, n_items] logits
+ * matrix. In-batch negatives (items = the batch's positives, targets NULL, col_bias = log q,
+ * col_ids = the item ids), mixed negatives (a shared pool appended to items) and the full softmax
+ * over a catalogue are this one call.
+ *
+ * Logit: z(r, j) = inv_temp · (queries[r] · items[j]) - col_bias[j] (col_bias == NULL: 0). The
+ *   dot product is an fp32 v_mfma_f32_32x32x2_f32 chain over the columns in a fixed order, the
+ *   same for every (r, j) whatever rows share a tile; columns [dim, ld) are never read.
+ * Target: t = targets[r] (int32), or r when targets == NULL.
+ * Columns kept: column j is left out of row r when col_ids != NULL, j != t and col_ids[j] ==
+ *   col_ids[t] (an accidental hit: the positive again among the negatives). The target column is
+ *   always kept, so a row has at least one term.
+ * Forward: lse[r] = log sum_j exp z(r, j) over the kept columns, by a running maximum (logits of
+ *   magnitude 1e4 neither overflow nor give NaN); loss[r] = lse[r] - z(r, t).
+ * Backward, g = grad_loss[r]: p(r, j) = exp(z(r, j) - lse[r]) for a kept column, 0 otherwise;
+ *   c(r, j) = (g · inv_temp) · (p(r, j) - [j == t]); grad_queries[r] = sum_j c(r, j) · items[j];
+ *   grad_items[j] = sum_r c(r, j) · queries[r]. Both are fully written ([n_queries, gq_ld] and
+ *   [n_items, gi_ld], columns [dim, ld) untouched), not accumulated; either may be NULL and is
+ *   then not computed. col_bias gets no gradient. Both recompute the logits from the rows.
+ * Bad targets: with targets == NULL, n_queries > n_items is RS_E_INVALID (row n_items has no
+ *   column). A targets[r] outside [0, n_items) is device data and cannot be seen by the host: that
+ *   row's loss and lse are NaN and it adds nothing to either gradient (its grad_queries row is 0).
+ * Non-finite values: a NaN in query row r makes loss[r], lse[r] and grad_queries[r] NaN and
+ *   reaches grad_items only through row r's terms c(r, j) · queries[r]. col_bias[j] = +inf on a
+ *   non-target column is the column left out (p = 0). A -inf logit adds exp(-inf) = 0 and a row
+ *   whose kept logits are all -inf has lse = -inf; a +inf logit gives lse = +inf (a NaN logit
+ *   NaN), and p = exp(z - lse) is then whatever IEEE makes of it: the NaN / inf pattern of every
+ *   output equals that of these formulas evaluated in float64.
+ * n_splits: 0 lets the call choose from the CU count (at most 16); 1 … 1024 forces that many
+ *   contiguous ranges of n / n_splits rows, the last taking the remainder, of the side a kernel
+ *   streams: the items for the forward and grad_queries, the queries for grad_items. Partial
+ *   (max, sum) pairs and partial gradient rows are merged in ascending range order.
+ * Determinism: no floating-point atomics; the outputs are a function of the inputs and of
+ *   n_splits. For a fixed n_splits >= 1 the bits of loss[r], lse[r] and grad_queries[r] do not
+ *   depend on which other query rows are in the call. No block waits for another and the host
+ *   never synchronises: both calls can be captured in a HIP graph on one stream.
+ * Limits: 1 <= dim <= 256, every ld >= dim, 1 <= n_items < 2^31. n_queries == 0 is a no-op. The
+ *   streamed rows are read with 16-byte loads when their base is 16-byte aligned and their ld and
+ *   dim are multiples of 4, else element by element (same bits, slower).
+ * Workspace: rs_item_softmax_workspace_size with the same four arguments serves both calls (0 for
+ *   sizes the calls refuse or need none for): three values per query row, three per (range,
+ *   query row) and, with more than one range, the partial gradient rows [ranges, rows, dim].
+ * Errors: RS_E_INVALID for null queries / items / loss / lse / grad_loss, grad_queries and
+ *   grad_items both NULL, dim or an ld out of range, a negative size, n_items == 0 with queries,
+ *   n_items >= 2^31, n_splits outside [0, 1024], a non-finite inv_temp, targets == NULL with
+ *   n_queries > n_items, a workspace that is too small. */
+size_t rs_item_softmax_workspace_size(int32_t n_queries, int64_t n_items, int32_t dim,
+                                      int32_t n_splits);
+int32_t rs_item_softmax_fwd(const float* queries, int64_t q_ld, int32_t n_queries,
+                            const float* items, int64_t i_ld, int64_t n_items, int32_t dim,
+                            const int32_t* targets, float inv_temp, const float* col_bias,
+                            const int64_t* col_ids, int32_t n_splits, float* loss, float* lse,
+                            void* workspace, size_t ws_bytes, void* stream);
+int32_t rs_item_softmax_bwd(const float* queries, int64_t q_ld, int32_t n_queries,
+                            const float* items, int64_t i_ld, int64_t n_items, int32_t dim,
+                            const int32_t* targets, float inv_temp, const float* col_bias,
+                            const int64_t* col_ids, int32_t n_splits, const float* lse,
+                            const float* grad_loss, float* grad_queries, int64_t gq_ld,
+                            float* grad_items, int64_t gi_ld, void* workspace, size_t ws_bytes,
+                            void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Ali-CCP and Amazon (DIEN) text → ids (esmm/process_public_dataset.py:40-153,
  * dien/util.py:4-37, dien/data_loader.py:27-63). Lines come from rs_line_index; each line is
  * str.strip()ped as the reference does.

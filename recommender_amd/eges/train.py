@@ -15,6 +15,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from ..functional import item_softmax_loss
 from ..optim import SparseAdam
 from ..steps import StaticKerasAdam
 from .model import EGES, GES, DeepWalk
@@ -60,13 +61,37 @@ def synthetic_batch(rng, batch, n_items, n_cat, n_brand, num_ns=5):
 class EGESStep:
     _static = None  # steps.StaticKerasAdam, built by the first static_step
 
-    def __init__(self, model, lr=1e-3):
+    def __init__(self, model, lr=1e-3, loss="sigmoid", temperature=1.0, log_q=None):
+        """loss: "sigmoid" (the reference's sigmoid CE over 1 + num_ns sampled logits) or
+        "inbatch" (softmax CE of every query against the batch's positives, by
+        functional.item_softmax_loss; the sampled negatives and the labels are not used).
+        log_q: optional float tensor [n_items], the log sampling probability of every item,
+        subtracted from the logits of the columns that hold it (the logQ correction)."""
+        if loss not in ("sigmoid", "inbatch"):
+            raise ValueError(f"EGESStep: loss must be sigmoid or inbatch, got {loss!r}")
         self.model = model
         self.opt = SparseAdam(model.tables(), lr=lr, mode="keras")
+        self.loss = loss
+        self.temperature = float(temperature)
+        self.log_q = log_q
+
+    def _loss(self, inputs, labels):
+        if self.loss == "sigmoid":
+            logits = self.model(inputs)
+            return F.binary_cross_entropy_with_logits(logits, labels)  # sigmoid CE, reduce_mean
+        *query, match = inputs
+        hidden = self.model.get_hidden(query[0] if len(query) == 1 else tuple(query))  # [B, 1, D]
+        pos = match[:, :1]
+        rows = self.model.output_embedding(pos)  # [B, 1, D]; its gradient: the sparse apply
+        ids = pos.reshape(-1)
+        B = hidden.shape[0]
+        log_q = None if self.log_q is None else self.log_q.index_select(0, ids.long())
+        return item_softmax_loss(hidden.reshape(B, -1), rows.reshape(B, -1), None,
+                                 temperature=self.temperature, log_q=log_q, item_ids=ids,
+                                 reduction="mean")
 
     def __call__(self, inputs, labels):
-        logits = self.model(inputs)
-        loss = F.binary_cross_entropy_with_logits(logits, labels)  # sigmoid CE, reduce_mean
+        loss = self._loss(inputs, labels)
         loss.backward()
         self.opt.step()
         return loss.detach()
@@ -79,8 +104,7 @@ class EGESStep:
         if self._static is None:
             self._static = StaticKerasAdam([], self.opt.tables, self.opt, self.opt.lr)
             self.opt_graph = self._static.opt
-        logits = self.model(inputs)
-        loss = F.binary_cross_entropy_with_logits(logits, labels)
+        loss = self._loss(inputs, labels)
         loss.backward()
         self._static.step()
         return loss.detach()
@@ -109,6 +133,8 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--seed", type=int, default=4)
     ap.add_argument("--n_items", type=int, default=63001)
+    ap.add_argument("--loss", default="sigmoid", choices=["sigmoid", "inbatch"])
+    ap.add_argument("--temperature", type=float, default=1.0)
     args = ap.parse_args(argv)
     rng = np.random.default_rng(args.seed)
     n_cat, n_brand = 801, 3000
@@ -118,7 +144,7 @@ def main(argv=None):
                               item2cat=(items * 2654435761) % n_cat,
                               item2brand=(items * 40503) % n_brand, seed=args.seed)
     model = build(args.model_type, args.n_items, n_cat, n_brand)
-    step = EGESStep(model)
+    step = EGESStep(model, loss=args.loss, temperature=args.temperature)
     t0 = time.perf_counter()
     for s in range(args.steps):
         *inp, lab = sampler.next_batch(args.train_batch_size, args.model_type)

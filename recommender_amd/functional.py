@@ -797,12 +797,12 @@ def _train_ws(B, dev):
     return L.workspace("dlrm.train", L.lib().rs_dlrm_train_workspace_size(B), dev)
 
 
-def _row_major(t: torch.Tensor, name: str):
+def _row_major(t: torch.Tensor, name: str, fn: str = "topk_inner_product"):
     """(fp32 tensor, row stride in floats) of a 2-D device tensor: a row-strided view (a column
     block of a wider matrix) is taken as it is, anything else is made contiguous."""
     L.require_device(t, name)
     if t.dim() != 2:
-        raise ValueError(f"topk_inner_product: {name} must be 2-D, got shape {tuple(t.shape)}")
+        raise ValueError(f"{fn}: {name} must be 2-D, got shape {tuple(t.shape)}")
     t = t.detach().float()
     if t.shape[0] > 1 and t.shape[1] > 0 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
         return t, t.stride(0)
@@ -904,6 +904,89 @@ def ivf_topk_inner_product(queries, probes, list_offsets, item_ids, vectors, k: 
            list_splits, L.ptr(idx), L.ptr(val), L.ptr(ws), ws.numel() if ws is not None else 0,
            L.stream_ptr(dev))
     return idx, val
+
+
+class _ItemSoftmax(torch.autograd.Function):
+    """loss [B] of rs_item_softmax_fwd; saves the rows and lse, and its backward is one
+    rs_item_softmax_bwd (which recomputes the logits tiles)."""
+
+    @staticmethod
+    def forward(ctx, queries, items, targets, inv_temp, log_q, item_ids, n_splits):
+        fn = "item_softmax_loss"
+        q, q_ld = _row_major(queries, "queries", fn)
+        x, i_ld = _row_major(items, "items", fn)
+        if q.shape[1] != x.shape[1]:
+            raise ValueError(f"{fn}: queries are {q.shape[1]} wide, items {x.shape[1]}")
+        if q.device != x.device:
+            raise ValueError(f"{fn}: queries and items on different devices")
+        dev = q.device
+        B, dim = q.shape
+        M = x.shape[0]
+
+        def vec(t, dtype, n, name):
+            if t is None:
+                return None
+            t = t.detach().to(device=dev, dtype=dtype).contiguous()
+            if t.shape != (n,):
+                raise ValueError(f"{fn}: {name} must have shape ({n},), got {tuple(t.shape)}")
+            return t
+
+        tg = vec(targets, torch.int32, B, "targets")
+        lq = vec(log_q, torch.float32, M, "log_q")
+        ids = vec(item_ids, torch.int64, M, "item_ids")
+        loss = torch.empty(B, device=dev)
+        lse = torch.empty(B, device=dev)
+        need = L.lib().rs_item_softmax_workspace_size(B, M, dim, n_splits)
+        ws = L.workspace("functional.item_softmax", need, dev) if need else None
+        L.call("rs_item_softmax_fwd", L.ptr(q), q_ld, B, L.ptr(x), i_ld, M, dim, L.ptr(tg),
+               inv_temp, L.ptr(lq), L.ptr(ids), n_splits, L.ptr(loss), L.ptr(lse), L.ptr(ws),
+               ws.numel() if ws is not None else 0, L.stream_ptr(dev))
+        ctx.save_for_backward(q, x, tg, lq, ids, lse)
+        ctx.args = (q_ld, i_ld, inv_temp, n_splits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        q, x, tg, lq, ids, lse = ctx.saved_tensors
+        q_ld, i_ld, inv_temp, n_splits = ctx.args
+        dev = q.device
+        B, dim = q.shape
+        M = x.shape[0]
+        want_q, want_x = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if B == 0 or not (want_q or want_x):
+            return (torch.zeros_like(q) if want_q else None,
+                    torch.zeros_like(x) if want_x else None, None, None, None, None, None)
+        g = grad_loss.detach().float().contiguous()
+        gq = torch.empty(B, dim, device=dev) if want_q else None
+        gx = torch.empty(M, dim, device=dev) if want_x else None
+        need = L.lib().rs_item_softmax_workspace_size(B, M, dim, n_splits)
+        ws = L.workspace("functional.item_softmax", need, dev) if need else None
+        L.call("rs_item_softmax_bwd", L.ptr(q), q_ld, B, L.ptr(x), i_ld, M, dim, L.ptr(tg),
+               inv_temp, L.ptr(lq), L.ptr(ids), n_splits, L.ptr(lse), L.ptr(g), L.ptr(gq), dim,
+               L.ptr(gx), dim, L.ptr(ws), ws.numel() if ws is not None else 0,
+               L.stream_ptr(dev))
+        return gq, gx, None, None, None, None, None
+
+
+def item_softmax_loss(queries, items, targets=None, *, temperature: float = 1.0, log_q=None,
+                      item_ids=None, reduction: str = "mean", n_splits: int = 0):
+    """Softmax cross-entropy of every query row [B, D] against the item rows [M, D], by
+    rs_item_softmax_fwd / _bwd: no [B, M] logits, softmax or gradient matrix in either direction.
+    Row r's positive is column targets[r] (None: column r, the in-batch form). The logit of
+    (r, j) is queries[r] · items[j] / temperature - log_q[j] (the logQ correction of sampled
+    negatives; no gradient); with item_ids [M], a column j != target that holds the target's id
+    (an accidental hit) is left out of row r. Gradients flow to queries and items (the items of
+    an Embedding lookup take theirs through the sparse apply). reduction: "mean", "sum" or
+    "none" (the [B] losses). n_splits: 0 = chosen from the CU count."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"item_softmax_loss: reduction must be mean, sum or none, got {reduction!r}")
+    if not temperature > 0:
+        raise ValueError(f"item_softmax_loss: temperature must be > 0, got {temperature}")
+    loss = _ItemSoftmax.apply(queries, items, targets, 1.0 / float(temperature), log_q, item_ids,
+                              int(n_splits))
+    if reduction == "none":
+        return loss
+    return loss.sum() if reduction == "sum" else loss.mean()
 
 
 def group_auc_counts(pred, label, group=None):

@@ -924,3 +924,22 @@ def binary_crossentropy(y_true, y_pred, from_logits: bool = False, epsilon: floa
         return F.binary_cross_entropy_with_logits(y_pred, y_true, reduction="none")
     p = torch.clamp(y_pred, epsilon, 1.0 - epsilon)
     return -(y_true * torch.log(p + epsilon) + (1.0 - y_true) * torch.log(1.0 - p + epsilon))
+
+
+class ItemSoftmaxLoss(nn.Module):
+    """Softmax cross-entropy of query rows against item rows (functional.item_softmax_loss): the
+    in-batch, mixed-negative and full-catalogue retrieval loss, with no [B, M] logits matrix.
+    forward(queries [B, D], items [M, D], targets=None, log_q=None, item_ids=None)."""
+
+    def __init__(self, temperature: float = 1.0, reduction: str = "mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"ItemSoftmaxLoss: reduction must be mean, sum or none, got {reduction!r}")
+        self.temperature = float(temperature)
+        self.reduction = reduction
+
+    def forward(self, queries, items, targets=None, log_q=None, item_ids=None):
+        from .functional import item_softmax_loss
+
+        return item_softmax_loss(queries, items, targets, temperature=self.temperature,
+                                 log_q=log_q, item_ids=item_ids, reduction=self.reduction)
