@@ -1209,8 +1209,9 @@ extern "C" int32_t rs_chain3_vec_compose(const float* K1, const int32_t* rows, i
 extern "C" int32_t rs_chain_aug_product(const float* M, int32_t ldm, int32_t m, const float* cin,
                                         const float* K, int32_t k, int32_t n, const float* b,
                                         float* out, void* stream) {
+  // (m == 0 with neither M nor cin: the staging loop's unguarded load would read through M)
   RS_CHECK_ARG(m >= 0 && m < kAugRows && k >= 1 && n >= 1 && ldm >= k && K && out &&
-                   (m == 0 || M) && (int64_t)(m + 1) * k <= kAugLds,
+                   (M || (m == 0 && cin)) && (int64_t)(m + 1) * k <= kAugLds,
                "rs_chain_aug_product: bad arguments");
   const unsigned g = (unsigned)ceil_div(n, 64);
   hipStream_t st = as_stream(stream);
