@@ -311,6 +311,88 @@ def topk_ip(iters, out, rounds=5):
     bench("eges_like", q, x, 10, None, 1)
 
 
+def topk_i8(iters, out, rounds=5):
+    """Two-stage retrieval (rs_topk_ip_i8, then rs_rerank_ip) against the exhaustive rs_topk_ip,
+    interleaved in one process: `rounds` rounds of the exact call, the int8 scan and the re-rank,
+    one launch each, timed with events; medians reported with every round next to them. The
+    quantisation of the catalogue (done once) is timed on its own. Per line: recall@10 of the
+    re-ranked result against the exact one, the bytes of codes + scales against the fp32
+    catalogue, and the scan's fraction of the 8 TB/s HBM peak counting one read of codes + scales
+    (its traffic floor: every 32-query row of blocks reads the catalogue again, mostly from cache).
+    Shapes: 65 536 queries x 2^20 items, k 10, kc 64, at D 64, 128 and 160; at D 160 also 256
+    queries (a serving batch) and kc 16. Data: a 4096-centre Gaussian mixture with unit-norm rows,
+    and unstructured normal rows. Queries are catalogue rows."""
+    from recommender_amd.functional import (quantize_rows_i8, rerank_inner_product,
+                                            topk_inner_product, topk_inner_product_i8)
+
+    N, k, kc = 1 << 20, 10, 64
+    hbm_bytes_per_s = 8.0e12
+    gen = torch.Generator(device=DEV).manual_seed(4)
+    s = torch.cuda.current_stream()
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record(s)
+        r = fn()
+        e1.record(s)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), r
+
+    def bench(name, x, Q, kc=kc):
+        D = x.shape[1]
+        q = x[torch.randint(0, N, (Q,), device=DEV, generator=gen)].contiguous()
+        quantize_rows_i8(x)  # warm-up
+        quant_ms, (codes, scales) = once(lambda: quantize_rows_i8(x))
+        cand = topk_inner_product_i8(q, codes, scales, kc, with_keys=False)[0]
+        fns = {"exact": lambda: topk_inner_product(q, x, k, with_scores=False)[0],
+               "scan": lambda: topk_inner_product_i8(q, codes, scales, kc, with_keys=False)[0],
+               "rerank": lambda: rerank_inner_product(q, x, cand, k, with_scores=False)[0]}
+        exact, got = fns["exact"](), fns["rerank"]()
+        recall = float((got[:, :, None] == exact[:, None, :]).any(1).float().mean())
+        times = {label: [] for label in fns}
+        for _ in range(rounds):
+            for label, fn in fns.items():
+                times[label].append(once(fn)[0])
+        me, ms, mr = (float(np.median(times[label])) for label in ("exact", "scan", "rerank"))
+        coded = codes.numel() + 4 * scales.numel()
+        line = {"kernel": "rs_topk_ip_i8 + rs_rerank_ip vs rs_topk_ip",
+                "config": {"data": name, "queries": Q, "items": N, "D": D, "k": k, "kc": kc},
+                "exact_ms": round(me, 3), "scan_ms": round(ms, 3), "rerank_ms": round(mr, 3),
+                "quantize_once_ms": round(quant_ms, 3),
+                "speedup": round(me / (ms + mr), 2),
+                "two_stage_below_fastest_exact_round": bool(ms + mr < min(times["exact"])),
+                "recall_at_10": round(recall, 4),
+                "coded_bytes": coded, "fp32_bytes": 4 * x.numel(),
+                "coded_fraction": round(coded / (4 * x.numel()), 4),
+                "scan_frac_of_hbm_peak_one_catalogue_read":
+                    round(coded / (ms * 1e-3) / hbm_bytes_per_s, 5),
+                "scan_int8_TOPS": round(2.0 * Q * N * D / (ms * 1e-3) / 1e12, 1),
+                "exact_rounds_ms": [round(t, 3) for t in times["exact"]],
+                "scan_rounds_ms": [round(t, 3) for t in times["scan"]],
+                "rerank_rounds_ms": [round(t, 3) for t in times["rerank"]]}
+        out.append(line)
+        print(json.dumps(line), flush=True)
+
+    for D in (64, 128, 160):
+        centres = torch.nn.functional.normalize(torch.randn(4096, D, device=DEV, generator=gen))
+        member = torch.randint(0, 4096, (N,), device=DEV, generator=gen)
+        x = centres[member] + 0.05 * torch.randn(N, D, device=DEV, generator=gen)
+        x = torch.nn.functional.normalize(x).contiguous()
+        del centres, member
+        bench("gaussian_mixture_4096", x, 65536)
+        if D == 160:
+            bench("gaussian_mixture_4096", x, 256)
+            bench("gaussian_mixture_4096", x, 65536, kc=16)  # fewer candidates: fewer compactions
+        del x
+        x = torch.randn(N, D, device=DEV, generator=gen)
+        bench("normal", x, 65536)
+        if D == 160:
+            bench("normal", x, 256)
+            bench("normal", x, 65536, kc=16)
+        del x
+
+
 def item_softmax(iters, out, rounds=3):
     """functional.item_softmax_loss (rs_item_softmax_fwd + _bwd, no [B, M] matrix) against the
     torch composition logsumexp(q @ v.T * inv_temp - log_q, 1) - diagonal under autograd, forward

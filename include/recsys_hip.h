@@ -1388,6 +1388,78 @@ int32_t rs_ivf_topk_ip(const float* queries, int64_t q_ld, int32_t n_queries,
                        void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Int8 candidate retrieval with an exact re-rank: the two-stage form of rs_topk_ip. Stage 1
+ * (rs_topk_ip_i8) scans the whole catalogue as symmetric per-row int8 codes on
+ * v_mfma_i32_32x32x32_i8 and keeps kc candidates per query; stage 2 (rs_rerank_ip) scores those
+ * few against the fp32 rows with rs_topk_ip's own chain and keeps k. Needs no trained index and
+ * works on any catalogue; the candidate step is approximate, the re-ranked scores are exact.
+ *
+ * Codes. A coded catalogue is codes int8 [n_items, c_ld] plus scales float32 [n_items]; a format
+ *   of its own, not RS_Q8 (whose bias would put a per-query float term into the integer score).
+ *   rs_i8_row_bytes(dim) = round_up(dim, 16) is the default c_ld (0 for dim <= 0).
+ *   Quantisation is fixed and bit-reproducible, per row: amax = max_d |x_d| (exact);
+ *   scale = amax / 127.f (IEEE division); scale == 0.f (a zero row, or an amax whose quotient
+ *   rounds to 0): all codes 0; otherwise code_d = (int8) min(max(rintf(x_d / scale), -127.f),
+ *   127.f) (IEEE division, ties to even; the clamp matters with a subnormal scale; -128 is never
+ *   produced). A row with a NaN or ±inf element is written as scale 0, codes 0 and sets
+ *   RS_ERRBIT_NONFINITE in err_flag (may be NULL). Bytes [dim, c_ld) are written as 0.
+ * rs_quantize_rows_i8: source row r at table + r * ld (floats), ld >= dim; c_ld >= dim,
+ *   c_ld % 4 == 0, codes 4-byte aligned. 16-byte stores are used when codes is 16-byte aligned
+ *   and c_ld % 16 == 0, else 4-byte stores. Alignment chooses the access width, never the bits.
+ *   n_rows == 0 is a no-op.
+ *
+ * rs_topk_ip_i8: out[r] = the kc items with the highest key.
+ *   Query codes: query row r (queries + r * q_ld, dim floats) is quantised inside the call by
+ *     exactly the rule above into cq[r, :]; a non-finite row has all codes 0 and there is no
+ *     flag. The query's scale is positive and common to the row, so it never enters the order
+ *     and is not used.
+ *   Integer score: I(r, i) = Σ_d cq[r, d] · codes[i, d], an exact integer whatever the order of
+ *     the sum. Any int8 value, -128 included, is legal in codes. |I| <= 256 · 128 · 128 = 2^22,
+ *     so (float) I is exact.
+ *   Key: key(r, i) = (float) I(r, i) * scales[i], one rounded fp32 multiply. scales is taken as
+ *     given: 0, negative, inf and NaN are legal; a NaN key ranks as -inf and is written as the
+ *     NaN it is.
+ *   Padding: bytes [dim, c_ld) of a code row and columns [dim, q_ld) of a query never influence
+ *     the result, whatever they hold.
+ *   Everything else is rs_topk_ip's, word for word, with key in place of the score: the
+ *     candidates and both exclusion forms, the order (key descending, then item ascending; -0
+ *     ties +0), the padding (-1, -inf), out_keys == NULL, n_splits (0 = chosen from the CU
+ *     count), the workspace (rs_topk_ip_i8_workspace_size with the same four arguments) and the
+ *     merge. Limits: 1 <= kc <= 64, 1 <= dim <= 256, q_ld >= dim, c_ld >= dim, c_ld % 4 == 0,
+ *     codes 4-byte aligned, n_items < 2^31. Code rows are read with 16-byte loads when codes is
+ *     16-byte aligned and c_ld % 16 == 0, else with 4-byte loads (same bits).
+ *   Determinism: the result is a function of the inputs only, independent of n_splits, n_queries
+ *     and of which rows share a tile. No block waits for another and the host never
+ *     synchronises: the call can be captured in a HIP graph.
+ *   Errors: rs_topk_ip's RS_E_INVALID cases, plus c_ld / alignment as above and a null scales.
+ *
+ * rs_rerank_ip: cand [n_queries, kc] int32 (contiguous) names kc candidates per query; entries
+ *   outside [0, n_items) are skipped (-1 is the padding the scan writes); a repeated id appears
+ *   repeated in the output. The score of (r, cand) is rs_topk_ip's ascending fmaf chain from
+ *   +0.f, bit for bit; order (score descending, then item ascending; NaN as -inf, written as
+ *   NaN) and padding (-1, -inf) are rs_topk_ip's. out_items / out_scores [n_queries, k], best
+ *   first; out_scores may be NULL. So the result equals rs_topk_ip's restricted to the candidate
+ *   set, bit for bit. 1 <= k <= kc <= 64, 1 <= dim <= 256, q_ld, i_ld >= dim, n_items < 2^31.
+ *   One wave per query; no workspace, no host synchronisation. Useful on its own, for instance to
+ *   re-rank rs_ivf_topk_ip's output.
+ *   Errors: RS_E_INVALID for null queries / cand / out_items (items too when n_items > 0), k, kc,
+ *   dim or ld out of range, a negative size, n_items >= 2^31. */
+size_t rs_i8_row_bytes(int32_t dim);
+int32_t rs_quantize_rows_i8(const float* table, int64_t ld, int64_t n_rows, int32_t dim,
+                            int8_t* codes, int64_t c_ld, float* scales, int32_t* err_flag,
+                            void* stream);
+size_t rs_topk_ip_i8_workspace_size(int32_t n_queries, int64_t n_items, int32_t kc,
+                                    int32_t n_splits);
+int32_t rs_topk_ip_i8(const float* queries, int64_t q_ld, int32_t n_queries, const int8_t* codes,
+                      int64_t c_ld, const float* scales, int64_t n_items, int32_t dim,
+                      int64_t excl_base, const int64_t* excl_indptr, const int32_t* excl_items,
+                      const int32_t* excl_one, int32_t kc, int32_t n_splits, int32_t* out_items,
+                      float* out_keys, void* workspace, size_t ws_bytes, void* stream);
+int32_t rs_rerank_ip(const float* queries, int64_t q_ld, int32_t n_queries, const float* items,
+                     int64_t i_ld, int64_t n_items, int32_t dim, const int32_t* cand, int32_t kc,
+                     int32_t k, int32_t* out_items, float* out_scores, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Softmax cross-entropy over item rows: the loss of query row r against every row of an item
  * matrix, with row t(r) the positive, forward and backward, with no [n_queries, n_items] logits
  * matrix. In-batch negatives (items = the batch's positives, targets NULL, col_bias = log q,

@@ -37,10 +37,15 @@ def item_hidden(model, item2cat=None, item2brand=None, batch: int = 65536) -> to
 
 
 def similar_items(hidden: torch.Tensor, query_items: torch.Tensor, k: int, index=None,
-                  nprobe: int = 8):
+                  nprobe: int = 8, n_candidates: int = 64):
     """index: a retrieval.IVFIndex over `hidden`: the search covers the nprobe lists nearest to
-    each query only (approximate; nprobe = index.nlist is exact). None: exhaustive."""
+    each query only (approximate; nprobe = index.nlist is exact). A retrieval.Int8Index: an int8
+    scan of every item keeps n_candidates per query, re-ranked exactly to k (nprobe is ignored).
+    None: exhaustive."""
     query_items = torch.as_tensor(query_items).to(hidden.device)
     if index is not None:
-        return index.search(hidden[query_items.long()], k, nprobe, exclude_one=query_items)
+        from ..retrieval import search_index
+
+        return search_index(index, hidden[query_items.long()], k, nprobe, n_candidates,
+                            exclude_one=query_items)
     return topk_inner_product(hidden[query_items.long()], hidden, k, exclude_one=query_items)

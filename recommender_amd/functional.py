@@ -838,6 +838,84 @@ def topk_inner_product(queries, items, k: int, exclude=None, exclude_base: int =
     return idx, val
 
 
+def i8_row_bytes(dim: int) -> int:
+    """The default row stride of an int8-coded catalogue of `dim` columns (rs_i8_row_bytes)."""
+    return int(L.lib().rs_i8_row_bytes(int(dim)))
+
+
+def quantize_rows_i8(items: torch.Tensor, c_ld: int | None = None,
+                     err_flag: torch.Tensor | None = None):
+    """(codes int8 [n, c_ld], scales fp32 [n]): the symmetric per-row int8 codes of an fp32
+    [n, dim] device tensor (rs_quantize_rows_i8), read where it lies when its rows are
+    row-strided. err_flag (device int32 [1]) gets RS_ERRBIT_NONFINITE when a row holds a NaN or an
+    infinity; that row is written as scale 0, codes 0."""
+    x, ld = _row_major(items, "items", "quantize_rows_i8")
+    n, dim = x.shape
+    c_ld = i8_row_bytes(dim) if c_ld is None else int(c_ld)
+    codes = torch.empty(n, max(c_ld, 0), dtype=torch.int8, device=x.device)
+    scales = torch.empty(n, device=x.device)
+    L.call("rs_quantize_rows_i8", L.ptr(x), ld, n, dim, L.ptr(codes), c_ld, L.ptr(scales),
+           L.ptr(err_flag), L.stream_ptr(x.device))
+    return codes, scales
+
+
+def topk_inner_product_i8(queries, codes, scales, kc: int, exclude=None, exclude_base: int = 0,
+                          exclude_one=None, with_keys: bool = True, n_splits: int = 0):
+    """(idx int32 [Q, kc], keys fp32 [Q, kc]) by rs_topk_ip_i8: per query row the kc items with the
+    highest key = (int8 query codes · int8 item codes) * item scale, best first, over a catalogue
+    coded by quantize_rows_i8 (codes int8 [n, c_ld], scales fp32 [n]); the width is the queries'.
+    The candidate stage of the two-stage search (rerank_inner_product is the second); the
+    exclusion arguments, the order and the padding are topk_inner_product's. No autograd."""
+    fn = "topk_inner_product_i8"
+    q, q_ld = _row_major(queries, "queries", fn)
+    L.require_device(codes, "codes")
+    L.require_device(scales, "scales")
+    if codes.dim() != 2 or codes.dtype != torch.int8:
+        raise ValueError(f"{fn}: codes must be int8 [n, c_ld]")
+    dev = q.device
+    if codes.device != dev or scales.device != dev:
+        raise ValueError(f"{fn}: queries, codes and scales on different devices")
+    codes = codes if codes.stride(1) == 1 and codes.shape[0] > 1 else codes.contiguous()
+    c_ld = codes.stride(0) if codes.shape[0] > 1 else max(codes.shape[1], 1)
+    sc = scales.detach().float().contiguous()
+    Q, dim = q.shape
+    n_items = codes.shape[0]
+    if sc.numel() != n_items or codes.shape[1] < dim:
+        raise ValueError(f"{fn}: need one scale per code row and code rows at least {dim} wide")
+    ip, it, one = _exclusion_args(fn, Q, exclude, exclude_base, exclude_one)
+    idx = torch.empty(Q, kc, dtype=torch.int32, device=dev)
+    val = torch.empty(Q, kc, device=dev) if with_keys else None
+    need = L.lib().rs_topk_ip_i8_workspace_size(Q, n_items, kc, n_splits)
+    ws = L.workspace("functional.topk_ip_i8", need, dev) if need else None
+    L.call("rs_topk_ip_i8", L.ptr(q), q_ld, Q, L.ptr(codes), c_ld, L.ptr(sc), n_items, dim,
+           exclude_base, L.ptr(ip), L.ptr(it), L.ptr(one), kc, n_splits, L.ptr(idx), L.ptr(val),
+           L.ptr(ws), ws.numel() if ws is not None else 0, L.stream_ptr(dev))
+    return idx, val
+
+
+def rerank_inner_product(queries, items, cand, k: int, with_scores: bool = True):
+    """(idx int32 [Q, k], scores fp32 [Q, k]) by rs_rerank_ip: the k best of each query's
+    candidates cand int32 [Q, kc] by the exact fp32 inner product (topk_inner_product's score,
+    order and padding, bit for bit). Entries outside [0, n_items) (-1) are skipped. No autograd."""
+    fn = "rerank_inner_product"
+    q, q_ld = _row_major(queries, "queries", fn)
+    x, i_ld = _row_major(items, "items", fn)
+    L.require_device(cand, "cand")
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"{fn}: queries are {q.shape[1]} wide, items {x.shape[1]}")
+    if cand.dim() != 2 or cand.shape[0] != q.shape[0]:
+        raise ValueError(f"{fn}: cand must be [Q, kc], got shape {tuple(cand.shape)}")
+    if x.device != q.device or cand.device != q.device:
+        raise ValueError(f"{fn}: queries, items and cand on different devices")
+    c = cand.to(torch.int32).contiguous()
+    Q, kc = c.shape
+    idx = torch.empty(Q, k, dtype=torch.int32, device=q.device)
+    val = torch.empty(Q, k, device=q.device) if with_scores else None
+    L.call("rs_rerank_ip", L.ptr(q), q_ld, Q, L.ptr(x), i_ld, x.shape[0], q.shape[1], L.ptr(c), kc,
+           k, L.ptr(idx), L.ptr(val), L.stream_ptr(q.device))
+    return idx, val
+
+
 def _exclusion_args(fn, Q, exclude, exclude_base, exclude_one):
     """(indptr int64, indices int32, one int32) device tensors (or None) of a top-k call."""
     ip = it = one = None

@@ -111,7 +111,8 @@ def masked_topk(scores: torch.Tensor, top_k: int, user_base: int = 0,
 
 def recommend(full_graph: HeteroGraph, top_k: int, item_reprs: torch.Tensor,
               user2item_etype=None, utype=None, timestamp: str = "timestamp",
-              batch_size: int = 32, fused: bool = False, index=None, nprobe: int = 8):
+              batch_size: int = 32, fused: bool = False, index=None, nprobe: int = 8,
+              n_candidates: int = 64):
     L.require_device(item_reprs, "item_reprs")
     reprs = item_reprs.float().contiguous()
     n_users, n_items = full_graph.n_users, reprs.shape[0]
@@ -119,7 +120,9 @@ def recommend(full_graph: HeteroGraph, top_k: int, item_reprs: torch.Tensor,
     if index is not None:
         if not fused:
             raise ValueError("recommend: index= goes with fused=True")
-        return index.search(reprs[latest.long()], top_k, nprobe,
+        from ..retrieval import search_index
+
+        return search_index(index, reprs[latest.long()], top_k, nprobe, n_candidates,
                             exclude=(full_graph.u2i_indptr, full_graph.u2i),
                             with_scores=False)[0]
     if fused:

@@ -30,7 +30,8 @@ under that global norm, layers.py:28-29); None leaves fc_2's output as it is.
 `python -m recommender_amd.pinsage.inference [--graph ml1m|ml20m] [--out reprs.npy]` runs it on
 the synthetic MovieLens graph of pinsage/train.py; `--neighbors K --neighbors-out nbrs.npy` adds
 each item's K nearest items by inner product (rs_topk_ip, the item itself excluded);
-`--neighbors-nlist N --neighbors-nprobe P` searches them through an IVF index (retrieval.py).
+`--neighbors-nlist N --neighbors-nprobe P` searches them through an IVF index (retrieval.py),
+`--neighbors-int8 KC` through the int8 candidate scan with an exact re-rank (retrieval.Int8Index).
 """
 from __future__ import annotations
 
@@ -225,9 +226,14 @@ def main(argv=None):
                     help="search the neighbours through an IVF index of N lists (0: exact)")
     ap.add_argument("--neighbors-nprobe", type=int, default=8, metavar="P",
                     help="lists searched per item with --neighbors-nlist")
+    ap.add_argument("--neighbors-int8", type=int, default=0, metavar="KC",
+                    help="search the neighbours in two stages: an int8 scan keeps KC candidates "
+                         "per item, the exact fp32 re-rank keeps K (0: exact)")
     args = ap.parse_args(argv)
     if bool(args.neighbors) != bool(args.neighbors_out):
         ap.error("--neighbors K and --neighbors-out FILE go together")
+    if args.neighbors_int8 and (args.neighbors_nlist > 0 or args.neighbors_int8 < args.neighbors):
+        ap.error("--neighbors-int8 KC needs KC >= K and excludes --neighbors-nlist")
     torch.manual_seed(args.seed)
     g, _, _ = build_dataset(ML1M if args.graph == "ml1m" else ML20M, args.seed)
     model = PinSageModel(g, g.itype, 2, 8, 32, 16)
@@ -256,6 +262,12 @@ def main(argv=None):
             index = IVFIndex.build(reprs, args.neighbors_nlist)
             nbrs, _ = index.search(reprs, args.neighbors, args.neighbors_nprobe, exclude_one=own,
                                    with_scores=False)
+        elif args.neighbors_int8 > 0:
+            from ..retrieval import Int8Index
+
+            nbrs, _ = Int8Index.from_float(reprs).search(reprs, args.neighbors,
+                                                         args.neighbors_int8, exclude_one=own,
+                                                         with_scores=False)
         else:
             nbrs, _ = topk_inner_product(reprs, reprs, args.neighbors, exclude_one=own,
                                          with_scores=False)

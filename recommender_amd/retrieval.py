@@ -14,13 +14,19 @@ IVFIndex.search           coarse step topk_inner_product(queries, centroids, npr
                           list scan rs_ivf_topk_ip. The result equals the exhaustive result
                           restricted to the probed lists, bit for bit; with nprobe = nlist it is
                           topk_inner_product's.
+
+Int8Index                 the other approximate form, with nothing to train: an
+                          int8 MFMA scan of the whole catalogue keeps n_candidates items per
+                          query (rs_topk_ip_i8), the exact fp32 re-rank keeps k (rs_rerank_ip).
+search_index              one search call for either index type.
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib as L
-from .functional import ivf_topk_inner_product, topk_inner_product
+from .functional import (ivf_topk_inner_product, quantize_rows_i8, rerank_inner_product,
+                         topk_inner_product, topk_inner_product_i8)
 
 _KEYS = ("centroids", "centroid_bias", "list_offsets", "item_ids", "vectors")
 
@@ -156,3 +162,63 @@ class IVFIndex:
     @property
     def list_sizes(self) -> torch.Tensor:
         return self.list_offsets[1:] - self.list_offsets[:-1]
+
+
+_I8_KEYS = ("codes", "scales", "vectors")
+
+
+class Int8Index:
+    """Two-stage search over the whole catalogue with no index to train: codes
+    int8 [n, c_ld] and scales fp32 [n] (quantize_rows_i8 of the item rows) for the int8 MFMA
+    candidate scan, vectors fp32 [n, dim] (the item rows themselves) for the exact re-rank."""
+
+    def __init__(self, codes, scales, vectors):
+        self.codes = codes
+        self.scales = scales
+        self.vectors = vectors
+
+    @classmethod
+    def from_float(cls, items: torch.Tensor) -> "Int8Index":
+        x = _items_2d(items, "Int8Index.from_float")
+        codes, scales = quantize_rows_i8(x)
+        return cls(codes, scales, x)
+
+    def search(self, queries, k: int, n_candidates: int = 64, exclude=None, exclude_base: int = 0,
+               exclude_one=None, with_scores: bool = True):
+        """(idx int32 [Q, k], scores fp32 [Q, k]) like topk_inner_product: the n_candidates best
+        items of every query by the int8 key (exclusions applied there), re-ranked to k by the
+        exact fp32 score. The scores are topk_inner_product's bits; the set is exact whenever the
+        true top k lie among the candidates."""
+        if not 1 <= k <= n_candidates:
+            raise ValueError(f"Int8Index.search: need 1 <= k <= n_candidates, got {k}, "
+                             f"{n_candidates}")
+        cand, _ = topk_inner_product_i8(queries, self.codes, self.scales, n_candidates,
+                                        exclude=exclude, exclude_base=exclude_base,
+                                        exclude_one=exclude_one, with_keys=False)
+        return rerank_inner_product(queries, self.vectors, cand, k, with_scores=with_scores)
+
+    def state_dict(self) -> dict:
+        return {k: getattr(self, k) for k in _I8_KEYS}
+
+    @classmethod
+    def from_state_dict(cls, sd: dict) -> "Int8Index":
+        missing = [k for k in _I8_KEYS if k not in sd]
+        if missing:
+            raise KeyError(f"Int8Index.from_state_dict: missing {missing}")
+        return cls(*(sd[k] for k in _I8_KEYS))
+
+    @property
+    def n_items(self) -> int:
+        return self.vectors.shape[0]
+
+    @property
+    def dim(self) -> int:
+        return self.vectors.shape[1]
+
+
+def search_index(index, queries, k: int, nprobe: int = 8, n_candidates: int = 64, **kw):
+    """index.search for either index type: an IVFIndex takes nprobe, an Int8Index n_candidates
+    (at least k) and ignores nprobe."""
+    if isinstance(index, Int8Index):
+        return index.search(queries, k, max(n_candidates, k), **kw)
+    return index.search(queries, k, nprobe, **kw)
